@@ -12,15 +12,23 @@ those are absent, by this script itself: it starts N fresh child processes befor
 touching any GPU and relays rank 0's line.  Each rank hashes its contiguous shard of the
 2^30 keys (no data-path collective: keys are independent, lib/k2hashfunc.cc:49-59); the
 line also times the RCCL gather of every shard's hashes to rank 0 (shard.gather_hashes).
-Every rank's shard is checked against the reference's digests
+With --full every rank's shard is checked against the reference's digests
 (tests/golden/digests.json, fixed32_1G chunks) outside the timed region.
 
-At N = 1 the line also carries secondary results (configs 3, 4 and 5, config 2 with the fused
-bucket index, RALLEDATA blobs, the k2himport TSV and mdbm scans + prehash of a file in HBM,
-and the host-memory path) and a CPU baseline: the reference's own hash path (oracle/_ref),
-timed on this host's cores.
+A plain run sets up, warms up, times exactly --steps launches, writes its outputs if
+--dump-outputs DIR is given and prints the line.  Everything else is behind --full: the
+digest checks of the timed path's hashes and, at N = 1, the secondary results (configs 3, 4
+and 5, config 2 with the fused bucket index, RALLEDATA blobs, the k2himport TSV and mdbm
+scans + prehash of a file in HBM, and the host-memory path) and a CPU baseline: the
+reference's own hash path (oracle/_ref), timed on this host's cores.
+
+--dump-outputs DIR writes what the last timed step computed (the arrays its caller receives:
+h1, and h2 / kindex / ckindex / blob / blob_off where the run produces them) as
+DIR/<name>.npy; see dump_outputs.  The inputs are a pure function of the arguments, so two
+builds run with the same arguments can be compared output for output.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config fixed32|csr|fixed4096|fixed32_1g|ralledata]
+                  [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -75,9 +83,14 @@ def parse(argv=None):
     p.add_argument("--index", action="store_true",
                    help="fused bucket-index epilogue (kindex + ckindex outputs, SURVEY 8f rank 1) with a "
                         "2^28-slot table: cur_mask 0x0FFFFFFF, collision_mask 0xF")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-secondary", action="store_true", help="N=1: skip the secondary configs")
-    p.add_argument("--no-verify", action="store_true", help="skip the digest checks")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the digest checks and, at N=1, the secondary configs "
+                        "and the CPU baseline (each can be dropped again with the --no-* options)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step computed as DIR/<name>.npy (rank 0's)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    p.add_argument("--no-secondary", action="store_true", help="--full at N=1: skip the secondary configs")
+    p.add_argument("--no-verify", action="store_true", help="--full: skip the digest checks")
     p.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL)")
     p.add_argument("--dist", action="store_true",
                    help="initialise torch.distributed even at world size 1 (under torchrun): rehearses the "
@@ -517,6 +530,35 @@ def timed(step, steps: int, warmup: int, warm_ms: float, world: int = 1, dist=No
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed, e0.elapsed_time(e1) / steps / 1e3, extra
+
+
+DUMP_SAMPLE = 1 << 19  # elements kept of each output array (<= 8 MiB per file)
+DUMP_SEED = 0x6B32686F75747075
+
+
+def dump_outputs(dirpath, arrays: dict) -> None:
+    """Write each output array of the last timed step as <dirpath>/<name>.npy.  An array of
+    more than DUMP_SAMPLE elements is cut to a fixed sample: DUMP_SAMPLE indices drawn once
+    from DUMP_SEED (a function of the array's length alone, sorted, so equal-length arrays
+    keep their rows aligned).  64-bit values (hashes, bucket positions, offsets) become
+    float64 rows [high 32 bits, low 32 bits], exact in that format; bytes become float32."""
+    import numpy as np
+    import torch
+
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype == np.uint8:
+            out = a.astype(np.float32)
+        else:
+            u = a.view(np.uint64)
+            out = np.stack([u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+        np.save(d / f"{name}.npy", out)
 
 
 def _profile(kind: str, name: str, keys: int | None):
@@ -1129,13 +1171,28 @@ def main():
     total_keys = (total if strong else n * world) * args.steps
     value = total_keys / elapsed
 
-    # --- verification against the reference's digests (outside the timed region) ---------
+    if args.dump_outputs and rank == 0:  # what the last timed step (args.steps - 1) wrote
+        last_set = (args.steps - 1) % nsets
+        if kind == "ralledata":
+            blob, boff, tot = sets[last_set][1]
+            dumped = {"blob": blob[:tot], "blob_off": boff}
+        else:
+            dumped = {"h1": outs[last_set][0]}
+            if args.second:
+                dumped["h2"] = outs[last_set][1]
+            if args.index:
+                dumped["kindex"], dumped["ckindex"] = idx[last_set]
+        dump_outputs(args.dump_outputs, dumped)
+        del dumped
+
+    # --- verification against the reference's digests (outside the timed region; --full) --
     verify = None
-    if not args.no_verify and strong:
+    do_verify = args.full and not args.no_verify
+    if do_verify and strong:
         chunks = golden_chunks(kind, shape, total)
         if chunks:
             verify = verify_sharded(outs[0][0], first, chunks, dist if use_dist else None, dev)
-    elif not args.no_verify and kind == "fixed" and not args.keys:
+    elif do_verify and kind == "fixed" and not args.keys:
         gname = {"fixed32": "fixed32_16M", "fixed4096": "fixed4096_1M"}[name]
         g = _golden()[gname]
         if name == "fixed32":  # set 0 of rank 0 is exactly the reference's 16M-key workload
@@ -1158,7 +1215,7 @@ def main():
             counts = [n] * world
         gsteps = max(3, min(10, args.steps // 10))
         gather, res = measure_gather(outs[0][0], counts, step, gsteps, dist, dev, torch.cuda.synchronize)
-        if rank == 0 and not args.no_verify and strong:
+        if rank == 0 and do_verify and strong:
             chunks = golden_chunks(kind, shape, total)
             gather["verify_root"] = verify_chunks(res, 0, chunks) if chunks else None
         else:
@@ -1169,11 +1226,12 @@ def main():
 
     secondary = None
     cpu = None
-    if rank == 0 and world == 1 and name == "fixed32" and not (args.index or args.second or args.keys):
+    plain_config2 = name == "fixed32" and not (args.index or args.second or args.keys)
+    if args.full and rank == 0 and world == 1 and plain_config2:
         if not args.no_secondary:
             del sets, outs
             torch.cuda.empty_cache()
-            vf = not args.no_verify
+            vf = do_verify
             secondary = {
                 "csr": secondary_csr(dev, 20, 60.0, vf, cpu=not args.no_cpu_baseline),
                 "fixed4096": secondary_fixed("fixed4096", dev, 20, 60.0, vf, "fixed4096_1M",
@@ -1209,6 +1267,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "warmup_extra_for_clock_ramp": extra,
+            "full": bool(args.full),
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",

@@ -161,7 +161,8 @@ def test_bench_rccl_path_one_rank():
 
 @pytest.mark.gpu
 def test_bench_n1_headline_verified():
-    line = _run(["--steps", "5", "--warmup", "2", "--warm-ms", "10", "--no-secondary", "--no-cpu-baseline"], 600)
+    line = _run(["--full", "--steps", "5", "--warmup", "2", "--warm-ms", "10", "--no-secondary",
+                 "--no-cpu-baseline"], 600)
     assert line["n_gpus"] == 1 and line["verify"]["ok"] is True
     assert 0 < line["roofline"]["frac"] < 1 and 0 < line["roofline"]["valu_frac"] < 1.2
 
@@ -248,7 +249,7 @@ def test_bench_csr_two_ranks_one_batch_cut_by_bytes():
     with the HIP kernel; the per-rank partial digests combine to the reference's and the
     gathered vector at rank 0 matches it too."""
     line = _run(["--gpus", "2", "--backend", "gloo", "--config", "csr", "--keys", "65536", "--steps", "5",
-                 "--warmup", "1", "--warm-ms", "5"], 600)
+                 "--warmup", "1", "--warm-ms", "5", "--full"], 600)
     g = line["gather"]
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["keys_total"] == 65536
     assert line["verify"]["ok"] is True and line["verify"]["chunks_checked"] == 1
@@ -261,6 +262,59 @@ def test_bench_csr_two_ranks_one_batch_cut_by_bytes():
 def test_bench_csr_rccl_one_rank():
     """The driver's command form with RCCL at one rank for the CSR strong path (--dist)."""
     line = _torchrun(1, ["--dist", "--config", "csr", "--keys", "65536", "--steps", "5", "--warmup", "1",
-                         "--warm-ms", "5"], 600)
+                         "--warm-ms", "5", "--full"], 600)
     assert line["gather"]["backend"] == "nccl" and line["verify"]["ok"] is True
     assert line["gather"]["verify_root"]["ok"] is True
+
+
+def test_dump_outputs_exact_and_sampled(tmp_path):
+    """--dump-outputs' writer on CPU tensors: 64-bit values round-trip exactly through the
+    float64 [high, low] rows, bytes through float32; a long array is cut to the same
+    DUMP_SAMPLE sorted rows on every call, and equal-length arrays keep their rows aligned."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    rng = np.random.default_rng(11)
+    h = rng.integers(0, 2**64, size=1001, dtype=np.uint64)
+    h[:3] = [0, 2**64 - 1, 2**63]
+    b = rng.integers(0, 256, size=777, dtype=np.uint8)
+    bench.dump_outputs(tmp_path / "a", {"h1": torch.from_numpy(h.view(np.int64).copy()),
+                                        "blob": torch.from_numpy(b.copy())})
+    got = np.load(tmp_path / "a" / "h1.npy")
+    assert got.dtype == np.float64 and got.shape == (1001, 2)
+    assert np.array_equal((got[:, 0].astype(np.uint64) << np.uint64(32)) | got[:, 1].astype(np.uint64), h)
+    blob = np.load(tmp_path / "a" / "blob.npy")
+    assert blob.dtype == np.float32 and np.array_equal(blob.astype(np.uint8), b)
+
+    n = bench.DUMP_SAMPLE + 12345
+    x = torch.arange(n, dtype=torch.int64)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, {"x": x, "y": x * 3})
+    xb, xc, yb = (np.load(tmp_path / d / f) for d, f in (("b", "x.npy"), ("c", "x.npy"), ("b", "y.npy")))
+    assert xb.shape == (bench.DUMP_SAMPLE, 2) and np.array_equal(xb, xc)
+    assert np.all(np.diff(xb[:, 1]) >= 0) and xb[:, 1].max() < n and np.array_equal(yb[:, 1], 3 * xb[:, 1])
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path, oracle):
+    """A plain run (no --full) times exactly --steps launches, checks and measures nothing
+    else, and --dump-outputs writes what the last timed step computed: with 4 steps over the
+    two rotated input sets that is set 1 (key bytes at stream offset keys x 32), whose h1 and
+    h2 must be the oracle's, bit for bit."""
+    import numpy as np
+
+    n = 65536 + 77
+    line = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--warm-ms", "5", "--keys", str(n), "--second",
+                 "--dump-outputs", str(tmp_path / "out")], 600)
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["full"] is False
+    assert abs(line["value"] - n * 4 / (line["ms_per_step"] * 4e-3)) <= 1e-6 * line["value"]
+    assert line["verify"] is None and line["cpu_baseline"] is None and "secondary" not in line
+    r1, r2 = oracle.hash_fixed(oracle.gen_bytes(n * 32, byte_off=n * 32), 32)
+    for name, ref in (("h1", r1), ("h2", r2)):
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == (n, 2)
+        assert np.array_equal((got[:, 0].astype(np.uint64) << np.uint64(32)) | got[:, 1].astype(np.uint64), ref)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The driver's own bench command (python bench.py, defaults) under rocprofv3 kernel and
+# The full bench line (python bench.py --full, other defaults) under rocprofv3 kernel and
 # marker traces.  bench.py (K2H_BENCH_MARKERS=1) wraps the synchronised timed region of the
 # headline and of every secondary in a roctx range "timed:<label>", so every figure in the
 # line is recomputed from the kernels inside its own range, in the same process
@@ -12,7 +12,7 @@ R=$(pwd)
 mkdir -p "$OUT"
 export K2H_BENCH_MARKERS=1
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --marker-trace --stats \
-   --output-format csv -d "$R/$OUT/trace" -o run -- python3 "$R/bench.py" "$@" > "$R/$OUT/bench.log" 2>&1) \
+   --output-format csv -d "$R/$OUT/trace" -o run -- python3 "$R/bench.py" --full "$@" > "$R/$OUT/bench.log" 2>&1) \
    || { echo "LINE PROFILE failed"; tail -20 "$R/$OUT/bench.log"; exit 1; }
 grep '^{' "$R/$OUT/bench.log" > "$R/$OUT/bench_line.json" || { echo "no bench line"; exit 1; }
 echo LINE_PROFILE_OK

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Recompute every bench-line figure from the profile of the same run.
 
-Input: a tools/profile_line.sh directory -- the driver's command (python bench.py) under
+Input: a tools/profile_line.sh directory -- the full bench line (python bench.py --full) under
 rocprofv3 --kernel-trace --marker-trace, with bench.py's roctx ranges "timed:<label>"
 around the synchronised timed region of the headline and of each secondary.
 
@@ -45,7 +45,7 @@ def main():
     kern = [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"]))
             for r in _rows("*kernel_trace.csv", src)]
     entries = {"headline": line, **(line.get("secondary") or {})}
-    out = {"tag": tag, "command": "python bench.py (the driver's default) under rocprofv3 --kernel-trace "
+    out = {"tag": tag, "command": "python bench.py --full under rocprofv3 --kernel-trace "
                                   "--marker-trace (tools/profile_line.sh)",
            "how": "frac_profile = the line's algorithmic bytes per launch / window / 8 TB/s; window = the dominant "
                   "kernel's average duration inside the entry's roctx range (import entries: range span / steps)",
