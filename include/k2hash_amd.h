@@ -199,7 +199,9 @@ int k2h_amd_build_ralledata_host(const void* keys, const uint64_t* key_off, cons
  *
  * k2h_amd_archive_scan walks a k2hash archive (K2HArchive::Save / Load,
  * lib/k2harchive.cc:82-383; record = packed 104-byte SCOM header + data,
- * lib/k2hcommand.h:64-79) as Load does and reports each record; recs may be NULL to
+ * lib/k2hcommand.h:64-79: char szCommand[16]; int64 type; uint64 key / val / skey / attr /
+ * exdata length; int64 key / val / skey / attrs / exdata position from the record's start;
+ * the next record starts 104 + the five lengths later) as Load does and reports each record; recs may be NULL to
  * count only.  k2h_amd_archive_prehash_host then hashes every record's key on the GPU
  * (and, if new_h1/new_h2 are given, the new key of each SCOM_RENAME record), so a
  * loader can have all hashes before applying record one.  Host pointers.
@@ -216,7 +218,7 @@ typedef struct k2h_amd_archive_rec {
   uint64_t offset; /* record start in the file */
   uint64_t key_off, key_len, val_off, val_len, skey_off, skey_len, attrs_off, attrs_len, exdata_off, exdata_len;
   /* absolute offsets in the file */
-  int32_t status;  /* 0, K2H_AMD_ARCHIVE_BAD_TYPE or K2H_AMD_ARCHIVE_TRUNCATED */
+  int32_t status;  /* 0, K2H_AMD_ARCHIVE_BAD_TYPE or K2H_AMD_ARCHIVE_TRUNCATED (device scan: or NO_MAGIC) */
   int32_t reserved;
 } k2h_amd_archive_rec;
 
@@ -225,6 +227,48 @@ int k2h_amd_archive_scan(const void* file, uint64_t size, k2h_amd_archive_rec* r
 int k2h_amd_archive_prehash_host(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t count,
                                  uint64_t* h1, uint64_t* h2, uint64_t* new_h1, uint64_t* new_h2, uint32_t flags,
                                  int device);
+
+/* The same scan and prehash for an archive already in device memory (file, recs, h1 ...:
+ * device pointers; count: host), with no host pass (k2hash_amd/csrc/k2h_archive_dev.hip).
+ *
+ * k2h_amd_archive_scan_device returns the records k2h_amd_archive_scan returns for the
+ * same bytes -- field for field, in file order, same count / cap convention (recs may be
+ * NULL to count only; more records than cap: K2H_AMD_EINVAL with *count set and nothing
+ * written past cap) -- and synchronises `stream`.  size < 104: *count = 0, no device work.
+ * It finds the record starts by the string every record's szCommand begins with,
+ * SCOM_COMSTR_PREFIX "\nK2H_" (lib/k2hcommand.h:36-45; K2HCommandArchive always writes it,
+ * lib/k2hcommand.cc:116-186), and resolves which of those places lie on the chain of
+ * records from offset 0; the same bytes inside a value are on no chain and change nothing.
+ * The one difference from the host scan: where the chain arrives at an offset at which a
+ * whole header fits but whose first five bytes are not that string, that record is
+ * reported with its fields filled in as usual and status K2H_AMD_ARCHIVE_NO_MAGIC (before
+ * BAD_TYPE and TRUNCATED), it is the last record and is counted, and the call returns
+ * K2H_AMD_OK.  (Load does not look at szCommand, so the host scan walks on; the reference's
+ * writer never produces such a file.)  A file whose offset 0 holds no prefix gives that one
+ * record.  K2H_AMD_EINVAL also for a file with 2^32 - 2 or more such places.
+ *
+ * k2h_amd_archive_prehash (async on `stream`) hashes every record's key as stored, read
+ * straight from the device-resident file, one lane per record: h1 = k2h_hash, h2 =
+ * k2h_second_hash (an empty key: 0); new_h1 / new_h2 the same of the exdata segment for
+ * SCOM_RENAME records (type 6), 0 for every other record.  h2, new_h1 and new_h2 may each
+ * be NULL.  A record with status != 0 gets zeros, and so does one whose key range is not
+ * inside [0, size) (recs are the caller's: off <= size && len <= size - off is checked
+ * again and nothing outside the file is read).  K2H_AMD_FLAG_STD_FNV selects the std-FNV
+ * seed; K2H_AMD_FLAG_CSTR returns K2H_AMD_EINVAL (archive keys are hashed as stored).
+ *
+ * k2h_amd_archive_scan_prehash_device does both in one call, the hashes from the kernel
+ * that writes the records; h1 (required with recs), h2, new_h1, new_h2 need room for cap
+ * entries; count / cap / errors as k2h_amd_archive_scan_device. */
+#define K2H_AMD_ARCHIVE_NO_MAGIC 3 /* device scan only: no "\nK2H_" where the chain arrives */
+
+int k2h_amd_archive_scan_device(const void* file, uint64_t size, k2h_amd_archive_rec* recs, uint64_t cap,
+                                uint64_t* count, void* stream);
+int k2h_amd_archive_prehash(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
+                            uint64_t* h1, uint64_t* h2, uint64_t* new_h1, uint64_t* new_h2, uint32_t flags,
+                            void* stream);
+int k2h_amd_archive_scan_prehash_device(const void* file, uint64_t size, k2h_amd_archive_rec* recs, uint64_t cap,
+                                        uint64_t* count, uint64_t* h1, uint64_t* h2, uint64_t* new_h1,
+                                        uint64_t* new_h2, uint32_t flags, void* stream);
 
 /* k2himport inputs (tests/k2himport.cc:74-117): k2h_amd_import_scan splits a TSV
  * (key TAB value NEWLINE) or mdbm_export file (five header lines ending "HEADER=END",

@@ -18,6 +18,7 @@ from .batch import FLAG_STD_FNV, _check_dev, _dev_ptr, _stream_handle, _torch
 FLAG_CSTR = _native.K2H_AMD_FLAG_CSTR
 SCOM_SET_ALL, SCOM_REPLACE_VAL, SCOM_REPLACE_SKEY, SCOM_DEL_KEY, SCOM_OW_VAL, SCOM_REPLACE_ATTRS, SCOM_RENAME = range(7)
 STATUS_OK, STATUS_BAD_TYPE, STATUS_TRUNCATED = 0, 1, 2
+STATUS_NO_MAGIC = 3  # scan_device only: the chain of records arrives where no "\nK2H_" starts
 
 # struct k2h_amd_archive_rec (include/k2hash_amd.h)
 REC_DTYPE = np.dtype([("type", "<i8"), ("offset", "<u8"), ("key_off", "<u8"), ("key_len", "<u8"),
@@ -59,6 +60,89 @@ def prehash(data, recs=None, rename: bool = False, std_fnv: bool = False, device
             ctypes.c_void_p(f.ctypes.data if f.size else 1), f.size, p(recs), n, p(h1), p(h2), p(nh1), p(nh2),
             FLAG_STD_FNV if std_fnv else 0, device))
     return (h1, h2, nh1, nh2) if rename else (h1, h2)
+
+
+REC_WORDS = REC_DTYPE.itemsize // 8  # a record as a row of 13 int64: status in the low half of column 12
+
+
+def scan_device(file, stream=None):
+    """scan for an archive already in device memory (uint8 device tensor), with no host
+    pass (k2h_amd_archive_scan_device).  Returns an (n, 13) int64 device tensor, each row one
+    struct k2h_amd_archive_rec (recs_to_numpy gives the REC_DTYPE view).  Where the chain of
+    records arrives at an offset that does not start with "\\nK2H_", the scan ends with one
+    record of status STATUS_NO_MAGIC (the host scan walks on)."""
+    torch = _torch()
+    _check_dev(file, "file", torch.uint8)
+    lib = _native.batch_lib()
+    fp = ctypes.c_void_p(file.data_ptr() or 1)
+    cnt = ctypes.c_uint64()
+    # one pass when the guess holds (records of >= 128 bytes on average); otherwise the call
+    # reports the count with K2H_AMD_EINVAL and a second pass fills exact storage
+    cap = max(1024, file.numel() // 128)
+    rc = 0
+    for _ in range(2):
+        recs = torch.empty((cap, REC_WORDS), dtype=torch.int64, device=file.device)
+        rc = lib.k2h_amd_archive_scan_device(fp, file.numel(), _dev_ptr(recs), cap, ctypes.byref(cnt),
+                                             _stream_handle(stream))
+        if not (rc == _native.K2H_AMD_EINVAL and cnt.value > cap):
+            break
+        cap = cnt.value
+    _native.check(rc)
+    return recs[: cnt.value]
+
+
+def recs_to_numpy(t) -> np.ndarray:
+    """The records of scan_device as a REC_DTYPE array on the host."""
+    a = np.ascontiguousarray(t.detach().cpu().numpy()).reshape(-1, REC_WORDS)
+    return a.view(REC_DTYPE).reshape(-1)
+
+
+def _check_recs(torch, recs):
+    _check_dev(recs, "recs", torch.int64)
+    if recs.dim() != 2 or recs.shape[1] != REC_WORDS or not recs.is_contiguous():
+        raise ValueError(f"recs must be a contiguous (n, {REC_WORDS}) int64 tensor")
+
+
+def prehash_device(file, recs, rename: bool = False, std_fnv: bool = False, stream=None):
+    """(h1, h2[, new_h1, new_h2]) int64 device tensors of every record's key hashed as
+    stored, from the device-resident file and the records of scan_device (asynchronous).
+    Zeros for a record whose status is not STATUS_OK or whose key range is not inside the
+    file; with rename=True also the new key (exdata) of SCOM_RENAME records."""
+    torch = _torch()
+    _check_dev(file, "file", torch.uint8)
+    _check_recs(torch, recs)
+    n = recs.shape[0]
+    out = [torch.empty(n, dtype=torch.int64, device=file.device) for _ in range(4 if rename else 2)]
+    ptrs = [_dev_ptr(x) for x in out] + [None] * (4 - len(out))
+    _native.check(_native.batch_lib().k2h_amd_archive_prehash(
+        ctypes.c_void_p(file.data_ptr() or 1), file.numel(), _dev_ptr(recs), n, *ptrs,
+        FLAG_STD_FNV if std_fnv else 0, _stream_handle(stream)))
+    return tuple(out)
+
+
+def scan_prehash_device(file, rename: bool = False, std_fnv: bool = False, stream=None):
+    """scan_device + prehash_device in one call (k2h_amd_archive_scan_prehash_device):
+    (recs, h1, h2[, new_h1, new_h2])."""
+    torch = _torch()
+    _check_dev(file, "file", torch.uint8)
+    lib = _native.batch_lib()
+    fp = ctypes.c_void_p(file.data_ptr() or 1)
+    flags = FLAG_STD_FNV if std_fnv else 0
+    cnt = ctypes.c_uint64()
+    cap = max(1024, file.numel() // 128)  # as scan_device: one pass when the guess holds
+    rc = 0
+    for _ in range(2):
+        recs = torch.empty((cap, REC_WORDS), dtype=torch.int64, device=file.device)
+        out = [torch.empty(cap, dtype=torch.int64, device=file.device) for _ in range(4 if rename else 2)]
+        ptrs = [_dev_ptr(x) for x in out] + [None] * (4 - len(out))
+        rc = lib.k2h_amd_archive_scan_prehash_device(fp, file.numel(), _dev_ptr(recs), cap, ctypes.byref(cnt), *ptrs,
+                                                     flags, _stream_handle(stream))
+        if not (rc == _native.K2H_AMD_EINVAL and cnt.value > cap):
+            break
+        cap = cnt.value
+    _native.check(rc)
+    n = cnt.value
+    return (recs[:n],) + tuple(x[:n] for x in out)
 
 
 def hash_ranges(base, starts, lens, second: bool = False, cstr: bool = False, std_fnv: bool = False, stream=None):

@@ -634,6 +634,50 @@ __attribute__((visibility("default"))) int k2h_amd_import_prehash(const void* fi
   return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "launch_import_prehash", e);
 }
 
+// k2hash archives in device memory (include/k2hash_amd.h section 5)
+__attribute__((visibility("default"))) int k2h_amd_archive_scan_device(const void* file, uint64_t size,
+                                                                       k2h_amd_archive_rec* recs, uint64_t cap,
+                                                                       uint64_t* count, void* stream) {
+  if (!count || (size && !file)) return fail(K2H_AMD_EINVAL, "archive_scan_device: NULL count/file");
+  if (size >= 104) K2H_GATE();  // a file without a whole header has no records and needs no device
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_archive_scan(file, size, recs, cap, count, (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EHIP || rc == K2H_AMD_ENOMEM) return fail(rc, "launch_archive_scan", e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "archive_scan_device: more records than cap, or too many candidates");
+}
+
+__attribute__((visibility("default"))) int k2h_amd_archive_prehash(const void* file, uint64_t size,
+                                                                   const k2h_amd_archive_rec* recs, uint64_t n,
+                                                                   uint64_t* h1, uint64_t* h2, uint64_t* new_h1,
+                                                                   uint64_t* new_h2, uint32_t flags, void* stream) {
+  if (flags & K2H_AMD_FLAG_CSTR) return fail(K2H_AMD_EINVAL, "archive_prehash: archive keys are hashed as stored");
+  if (n == 0) return K2H_AMD_OK;
+  if (!recs || !h1 || (size && !file)) return fail(K2H_AMD_EINVAL, "archive_prehash: NULL file/recs/h1");
+  K2H_GATE();
+  k2h::ArchiveHashOut out;
+  out.h1 = h1, out.h2 = h2, out.new_h1 = new_h1, out.new_h2 = new_h2;
+  hipError_t e = k2h::launch_archive_prehash(file, size, recs, n, seed_for(flags), out, (hipStream_t)stream);
+  return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "launch_archive_prehash", e);
+}
+
+__attribute__((visibility("default"))) int k2h_amd_archive_scan_prehash_device(
+    const void* file, uint64_t size, k2h_amd_archive_rec* recs, uint64_t cap, uint64_t* count, uint64_t* h1,
+    uint64_t* h2, uint64_t* new_h1, uint64_t* new_h2, uint32_t flags, void* stream) {
+  if (flags & K2H_AMD_FLAG_CSTR)
+    return fail(K2H_AMD_EINVAL, "archive_scan_prehash_device: archive keys are hashed as stored");
+  if (!count || (size && !file)) return fail(K2H_AMD_EINVAL, "archive_scan_prehash_device: NULL count/file");
+  if (recs && cap && !h1) return fail(K2H_AMD_EINVAL, "archive_scan_prehash_device: NULL h1");
+  if (size >= 104) K2H_GATE();
+  k2h::ArchiveHashOut out;
+  out.h1 = h1, out.h2 = h2, out.new_h1 = new_h1, out.new_h2 = new_h2;
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_archive_scan(file, size, recs, cap, count, (hipStream_t)stream, &e,
+                                    (recs && cap) ? &out : nullptr, seed_for(flags));
+  if (rc == K2H_AMD_EHIP || rc == K2H_AMD_ENOMEM) return fail(rc, "launch_archive_scan", e);
+  return rc == K2H_AMD_OK ? rc
+                          : fail(rc, "archive_scan_prehash_device: more records than cap, or too many candidates");
+}
+
 // ---------------------------------------------------------------------------
 // RALLEDATA producer (include/k2hash_amd.h section 4)
 // ---------------------------------------------------------------------------

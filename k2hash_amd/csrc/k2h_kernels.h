@@ -110,6 +110,21 @@ int launch_import_scan(const void* file, uint64_t size, int format, k2h_amd_impo
 hipError_t launch_import_prehash(const void* file, uint64_t size, const k2h_amd_import_rec* recs, uint64_t n,
                                  uint64_t seed, uint64_t* h1, uint64_t* h2, hipStream_t stream);
 
+// k2hash archives already in device memory (k2h_archive_dev.hip).  launch_archive_scan
+// returns a K2H_AMD_* code (the HIP error in *herr) and synchronises the stream.
+// hash != NULL: each written record's key (and, where new_h1 / new_h2 are given, the new key
+// of each SCOM_RENAME record) is also hashed as stored, by the kernel that writes the record.
+struct ArchiveHashOut {
+  uint64_t* h1 = nullptr;  // required; the others may be null
+  uint64_t* h2 = nullptr;
+  uint64_t* new_h1 = nullptr;
+  uint64_t* new_h2 = nullptr;
+};
+int launch_archive_scan(const void* file, uint64_t size, k2h_amd_archive_rec* recs, uint64_t cap, uint64_t* count,
+                        hipStream_t stream, hipError_t* herr, const ArchiveHashOut* hash = nullptr, uint64_t seed = 0);
+hipError_t launch_archive_prehash(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
+                                  uint64_t seed, const ArchiveHashOut& hash, hipStream_t stream);
+
 // S_p = seed * P^-p (p = 0..15): start states for end-aligned chunking (k2h_csr.hip).
 struct SpadTable {
   uint64_t v[16];
