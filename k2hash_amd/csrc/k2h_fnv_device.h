@@ -290,41 +290,76 @@ __device__ __forceinline__ void fnv_key32_x2(const void* src, uint64_t* dst1, ui
                : K2H_X_CLOBBERS);
 }
 
-// Two 32-byte keys per lane, h1 only, as ONE statement: the four nt loads issued together
-// (key 0 into v[40:47], key 1 into v[32:39]), key 0 hashed as soon as ITS two loads have
-// landed (vmcnt(2): loads return in order) while key 1's are still in flight, key 1 hashed
-// in place (no copies into the window), both hashes stored at the end.  hipcc, given the
-// loads as code, waited for all four before the first hash (vmcnt(0)).
+// NK (3 or 4) 32-byte keys per lane, h1 only, as ONE statement over a wave's block of
+// 64 NK keys: lane t hashes keys 64 j + t of the block, j < NK.  Every load and store is
+// addressed as a wave-uniform SGPR base + one 32-bit lane offset + an immediate, so the
+// only address VALU ops of the wave are the two lane offsets (voff = 32 t, doff = 8 t):
+//   key j   at sbase - 4096 + 2048 j + voff   (sbase = the block's first key + 4096: the
+//                                              13-bit signed immediate cannot reach +4096)
+//   hash j  at dbase + 512 j + doff
+// All 2 NK nt loads are issued first; key j is hashed in the registers it was loaded into
+// as soon as its own two loads are in (vmcnt(2 (NK-1-j)); loads return in order), its hash
+// parked in a spare pair while the next key runs, and all hashes stored at the end (a
+// store among the loads would count in vmcnt out of order).  Registers: key 0 v[40:47],
+// key 1 v[32:39], key 2 v[24:31], key 3 v[16:23]; window v48-v58 as above; parked hashes
+// v[62:63], v[60:61], v[14:15], the last key's stays in v[48:49].  The caller guarantees
+// that all 64 NK keys exist.
+#define K2H_X_KEY(A, B, C, D, E, F, G, H)                                                           \
+  K2H_X_PAIR("v" #A, "v" #B, "v[" #A ":" #B "]") K2H_X_PAIR("v" #C, "v" #D, "v[" #C ":" #D "]")     \
+      K2H_X_PAIR("v" #E, "v" #F, "v[" #E ":" #F "]") K2H_X_PAIR("v" #G, "v" #H, "v[" #G ":" #H "]")
+#define K2H_Q_LOAD(A, B, C, D, O0, O1)                                                  \
+  "global_load_dwordx4 v[" #A ":" #B "], %[voff], %[sbase] offset:" #O0 " nt\n\t"       \
+  "global_load_dwordx4 v[" #C ":" #D "], %[voff], %[sbase] offset:" #O1 " nt\n\t"
+#define K2H_Q_SEED "v_mov_b32 v48, %[slo]\n\tv_mov_b32 v49, %[shi]\n\t"
+#define K2H_Q_PARK(LO, HI, CNT) \
+  "v_mov_b32 " LO ", v48\n\tv_mov_b32 " HI ", v49\n\t" K2H_Q_SEED "s_waitcnt vmcnt(" #CNT ")\n\t"
+#define K2H_Q_STORE(PAIR, O) "global_store_dwordx2 %[doff], " PAIR ", %[dbase] offset:" #O " nt\n\t"
+#define K2H_Q_INPUTS                                                                                            \
+  [voff] "v"(voff), [sbase] "s"(sbase), [doff] "v"(doff), [dbase] "s"(dbase), [slo] "s"((uint32_t)seed),        \
+      [shi] "s"((uint32_t)(seed >> 32)), [p] "s"(kPrimeLo), [sel] "s"(kSmearSel)
+#define K2H_Q_CLOBBERS3                                                                                         \
+  "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", \
+      K2H_X_CLOBBERS, "v62", "v63"
+template <int NK>
+__device__ __forceinline__ void fnv_key32_quad_x(uint32_t voff, const void* sbase, uint32_t doff, uint64_t* dbase,
+                                                 uint64_t seed) {
+  static_assert(NK == 3 || NK == 4, "three or four keys per lane");
+  if constexpr (NK == 4) {
+    asm volatile(K2H_Q_LOAD(40, 43, 44, 47, -4096, -4080) K2H_Q_LOAD(32, 35, 36, 39, -2048, -2032)
+                     K2H_Q_LOAD(24, 27, 28, 31, 0, 16) K2H_Q_LOAD(16, 19, 20, 23, 2048, 2064)
+                         K2H_Q_SEED "v_mov_b32 v50, 0\n\t"
+                 "s_waitcnt vmcnt(6)\n\t" K2H_X_KEY(40, 41, 42, 43, 44, 45, 46, 47)
+                 K2H_Q_PARK("v62", "v63", 4) K2H_X_KEY(32, 33, 34, 35, 36, 37, 38, 39)
+                 K2H_Q_PARK("v60", "v61", 2) K2H_X_KEY(24, 25, 26, 27, 28, 29, 30, 31)
+                 K2H_Q_PARK("v14", "v15", 0) K2H_X_KEY(16, 17, 18, 19, 20, 21, 22, 23)
+                 K2H_Q_STORE("v[62:63]", 0) K2H_Q_STORE("v[60:61]", 512) K2H_Q_STORE("v[14:15]", 1024)
+                 K2H_Q_STORE("v[48:49]", 1536) "s_nop 1\n\t"
+                 :
+                 : K2H_Q_INPUTS
+                 : "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", K2H_Q_CLOBBERS3);
+  } else {
+    asm volatile(K2H_Q_LOAD(40, 43, 44, 47, -4096, -4080) K2H_Q_LOAD(32, 35, 36, 39, -2048, -2032)
+                     K2H_Q_LOAD(24, 27, 28, 31, 0, 16) K2H_Q_SEED "v_mov_b32 v50, 0\n\t"
+                 "s_waitcnt vmcnt(4)\n\t" K2H_X_KEY(40, 41, 42, 43, 44, 45, 46, 47)
+                 K2H_Q_PARK("v62", "v63", 2) K2H_X_KEY(32, 33, 34, 35, 36, 37, 38, 39)
+                 K2H_Q_PARK("v60", "v61", 0) K2H_X_KEY(24, 25, 26, 27, 28, 29, 30, 31)
+                 K2H_Q_STORE("v[62:63]", 0) K2H_Q_STORE("v[60:61]", 512) K2H_Q_STORE("v[48:49]", 1024) "s_nop 1\n\t"
+                 :
+                 : K2H_Q_INPUTS
+                 : K2H_Q_CLOBBERS3);
+  }
+}
+
+// Two 32-byte keys per lane as ONE statement: the four nt loads issued together (key 0
+// into v[40:47], key 1 into v[32:39]), key 0 hashed as soon as ITS two loads have landed
+// (vmcnt(2): loads return in order) while key 1's are still in flight, key 1 hashed in
+// place (no copies into the window).  hipcc, given the loads as code, waited for all four
+// before the first hash (vmcnt(0)).  The hashes are returned in registers (stored by the
+// caller, e.g. with the fused bucket-index epilogue); H2 also returns each key's second hash
+// (the state before its last byte: key 0's parked in v55/v59 while key 1 is hashed).
 #define K2H_X_KEY1 \
   K2H_X_PAIR("v32", "v33", "v[32:33]") K2H_X_PAIR("v34", "v35", "v[34:35]") K2H_X_PAIR("v36", "v37", "v[36:37]") \
       K2H_X_PAIR("v38", "v39", "v[38:39]")
-__device__ __forceinline__ void fnv_key32_pair_x(const void* src0, const void* src1, uint64_t* dst0, uint64_t* dst1,
-                                                 uint64_t seed) {
-  asm volatile("global_load_dwordx4 v[40:43], %[s0], off nt\n\t"
-               "global_load_dwordx4 v[44:47], %[s0], off offset:16 nt\n\t"
-               "global_load_dwordx4 v[32:35], %[s1], off nt\n\t"
-               "global_load_dwordx4 v[36:39], %[s1], off offset:16 nt\n\t"
-               "v_mov_b32 v48, %[slo]\n\t"
-               "v_mov_b32 v49, %[shi]\n\t"
-               "v_mov_b32 v50, 0\n\t"
-               "s_waitcnt vmcnt(2)\n\t" K2H_X_BODY K2H_X_PAIR("v46", "v47", "v[46:47]")
-               "v_mov_b32 v62, v48\n\t"
-               "v_mov_b32 v63, v49\n\t"
-               "v_mov_b32 v48, %[slo]\n\t"
-               "v_mov_b32 v49, %[shi]\n\t"
-               "s_waitcnt vmcnt(0)\n\t" K2H_X_KEY1
-               "global_store_dwordx2 %[d0], v[62:63], off nt\n\t"
-               "global_store_dwordx2 %[d1], v[48:49], off nt\n\t"
-               "s_nop 1\n\t"
-               :
-               : [s0] "v"(src0), [s1] "v"(src1), [d0] "v"(dst0), [d1] "v"(dst1), [slo] "s"((uint32_t)seed),
-                 [shi] "s"((uint32_t)(seed >> 32)), [p] "s"(kPrimeLo), [sel] "s"(kSmearSel)
-               : "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", K2H_X_CLOBBERS, "v62", "v63");
-}
-
-// The same two-key statement with the hashes returned in registers (stored by the caller,
-// e.g. with the fused bucket-index epilogue); H2 also returns each key's second hash (the
-// state before its last byte: key 0's parked in v55/v59 while key 1 is hashed).
 #define K2H_X_KEY1_LAST \
   K2H_X_PAIR("v32", "v33", "v[32:33]") K2H_X_PAIR("v34", "v35", "v[34:35]") K2H_X_PAIR("v36", "v37", "v[36:37]") \
       K2H_X_PAIR_LAST("v38", "v39", "v[38:39]")

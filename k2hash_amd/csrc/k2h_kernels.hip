@@ -108,29 +108,25 @@ __global__ __launch_bounds__(256) void fill_zero_kernel(uint64_t* __restrict__ p
 
 static inline unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
-// fixed32 (BASELINE config 2): 32-byte keys at a 16-aligned base.  One-wave blocks, KPT
-// keys per lane: block b owns keys [b*64*KPT, (b+1)*64*KPT), lane t hashes keys
+// fixed32 with h2 and / or the fused index: 32-byte keys at a 16-aligned base.  One-wave
+// blocks, KPT keys per lane: block b owns keys [b*64*KPT, (b+1)*64*KPT), lane t hashes keys
 // b*64*KPT + 64 j + t.  All 2*KPT nontemporal loads are issued before the first hash, so
 // each wave keeps KPT*2 KiB in flight while it computes; one-wave blocks let a finished
 // wave's slot be refilled at once (round-1 A/B: KPT = 2, 64-thread blocks, nt loads and
 // stores).  The second key's registers sit below the asm window, so
-// the kernel stays at 59 VGPRs (8 waves/SIMD).  The headline form (KPT = 2, h1 only) is one
-// asm statement per lane (fnv_key32_pair_x): hipcc waited for all four loads before the
-// first hash; there key 0 is hashed once its own two loads are in (vmcnt(2)) and key 1 in
-// the registers it was loaded into (round 3: 118.0 -> 113.7 us on config 2 in A/B,
-// profiles/r03af_fixed32_ab.txt).
+// the kernel stays within 64 VGPRs (8 waves/SIMD).  KPT = 2 is one asm statement per lane
+// (fnv_key32_pair_r): hipcc waited for all four loads before the first hash; there key 0 is
+// hashed once its own two loads are in (vmcnt(2)) and key 1 in the registers it was loaded
+// into (round 3: 118.0 -> 113.7 us on config 2 in A/B, profiles/r03af_fixed32_ab.txt).
+// The h1-only form without the index is fnv_fixed32_quad_kernel below.
 template <bool H2, int KPT, bool EPI = false>
 __global__ __launch_bounds__(64) void fnv_fixed32_kpt_kernel(const uint4* __restrict__ keys, uint64_t n,
                                                              uint64_t seed, uint64_t* __restrict__ h1,
                                                              uint64_t* __restrict__ h2, BucketParams bp = {}) {
   constexpr int BS = 64;
   const uint64_t base = (uint64_t)blockIdx.x * (BS * KPT) + threadIdx.x;
-  if constexpr (KPT == 2 && !H2 && !EPI) {  // the headline form: one asm statement per lane
-    // lanes past the end re-hash key n-1 and store its (identical) hash to h1[n-1]
-    const uint64_t i0 = base < n ? base : n - 1, i1 = base + BS < n ? base + BS : n - 1;
-    fnv_key32_pair_x(keys + 2 * i0, keys + 2 * i1, h1 + i0, h1 + i1, seed);
-    return;
-  } else if constexpr (KPT == 2) {  // h2 and / or the fused index: the same statement, hashes returned
+  if constexpr (KPT == 2) {  // one asm statement per lane, hashes returned in registers
+    // lanes past the end re-hash key n-1 and store nothing
     const uint64_t i0 = base < n ? base : n - 1, j1 = base + BS, i1 = j1 < n ? j1 : n - 1;
     uint64_t r0, r1, s0, s1;
     fnv_key32_pair_r<H2>(keys + 2 * i0, keys + 2 * i1, seed, r0, r1, s0, s1);
@@ -172,6 +168,31 @@ __global__ __launch_bounds__(64) void fnv_fixed32_kpt_kernel(const uint4* __rest
   }
 }
 
+// fixed32, h1 only (the headline form): one-wave blocks, NK keys per lane; block b owns keys
+// [64 NK b, 64 NK (b+1)).  A block whose keys all exist (b < nfull = n / (64 NK), a scalar
+// compare) takes the NK-key statement fnv_key32_quad_x: the block's key and hash bases are
+// wave-uniform (SGPR arithmetic on blockIdx), the lane offsets 32 t and 8 t are the only
+// address VALU ops of the wave, and the wave keeps 2 NK KiB in flight.  The one block that
+// straddles n hashes its keys below n one at a time (fnv_key32_x) and touches nothing at
+// or past n.  64 VGPRs; 17 VALU ops per four keys that are not hash steps (the two-key
+// kernel: 25 per two keys).  NK = 4 against the two-key kernel on config 2, one process, interleaved:
+// 112.3 vs 116.5 us, below it in every round; NK = 3: 114.0 us
+// (profiles/r08_fixed32_quad_ab.json).
+constexpr int kFixed32QuadKeys = 4;
+template <int NK>
+__global__ __launch_bounds__(64) void fnv_fixed32_quad_kernel(const uint4* __restrict__ keys, uint32_t nfull,
+                                                              uint64_t n, uint64_t seed, uint64_t* __restrict__ h1) {
+  constexpr uint32_t BK = 64 * NK;  // keys per block
+  const uint32_t t = threadIdx.x;
+  if (blockIdx.x < nfull) {
+    const uint64_t first = (uint64_t)blockIdx.x * BK;
+    fnv_key32_quad_x<NK>(t * 32u, (const uint8_t*)(keys + 2 * first) + 4096, t * 8u, h1 + first, seed);
+    return;
+  }
+#pragma unroll 1
+  for (uint64_t i = (uint64_t)blockIdx.x * BK + t; i < n; i += 64) fnv_key32_x(keys + 2 * i, h1 + i, seed);
+}
+
 hipError_t launch_bucket_index(const uint64_t* h1, uint64_t n, const BucketParams& bp, hipStream_t stream) {
   if (n == 0 || !(bp.kindex || bp.ckindex || bp.found)) return hipSuccess;
   bucket_index_kernel<<<grid_for(n), 256, 0, stream>>>(h1, n, bp);
@@ -179,8 +200,9 @@ hipError_t launch_bucket_index(const uint64_t* h1, uint64_t n, const BucketParam
 }
 
 // Default kernel per shape (the product path).  32-byte keys at a 16-aligned base: one-wave
-// blocks, two keys per lane with all four loads issued before the first hash (a wave keeps
-// 4 KiB in flight and half as many waves need dispatching; round-1 A/B).
+// blocks with all loads issued before the first hash; h1 alone takes four keys per lane
+// (fnv_fixed32_quad_kernel: 8 KiB in flight per wave), h2 and / or the fused index two
+// (fnv_fixed32_kpt_kernel: 4 KiB).
 // Other lengths: up to 32 B the per-lane tail loop, below 128 B
 // per-lane direct 16-byte loads, from 128 B on the line-DMA kernel (multiples of 128 B at a
 // 128-aligned base) or the cooperative line ring.
@@ -201,8 +223,13 @@ hipError_t launch_fixed(const void* keys, uint64_t key_len, uint64_t n, uint64_t
       if (h2) fnv_fixed32_kpt_kernel<true, 2, true><<<g, 64, 0, stream>>>(k, n, seed, h1, h2, *bp);
       else fnv_fixed32_kpt_kernel<false, 2, true><<<g, 64, 0, stream>>>(k, n, seed, h1, nullptr, *bp);
     } else {
-      if (h2) fnv_fixed32_kpt_kernel<true, 2><<<g, 64, 0, stream>>>(k, n, seed, h1, h2);
-      else fnv_fixed32_kpt_kernel<false, 2><<<g, 64, 0, stream>>>(k, n, seed, h1, nullptr);
+      if (h2) {
+        fnv_fixed32_kpt_kernel<true, 2><<<g, 64, 0, stream>>>(k, n, seed, h1, h2);
+      } else {
+        constexpr unsigned bk = 64 * kFixed32QuadKeys;
+        fnv_fixed32_quad_kernel<kFixed32QuadKeys>
+            <<<(unsigned)((n + bk - 1) / bk), 64, 0, stream>>>(k, (uint32_t)(n / bk), n, seed, h1);
+      }
     }
     return hipGetLastError();
   }

@@ -49,6 +49,40 @@ __global__ __launch_bounds__(256) void k_read(const uint4* __restrict__ keys, ui
   uint32_t v = a.x ^ a.y ^ a.z ^ a.w ^ b.x ^ b.y ^ b.z ^ b.w;
   if (v == 0x12345678u) h1[i] = v;
 }
+// Eight nt loads of a wave's four key rows, each a wave-uniform base + 32-bit lane offset +
+// immediate (the base biased by 4 KiB so that the 13-bit signed immediate reaches every row).
+typedef uint32_t v4u_q __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void load_quad(const void* sbase, uint32_t voff, v4u_q (&x)[4], v4u_q (&y)[4]) {
+  asm volatile("global_load_dwordx4 %0, %8, %9 offset:-4096 nt\n\t"
+               "global_load_dwordx4 %1, %8, %9 offset:-4080 nt\n\t"
+               "global_load_dwordx4 %2, %8, %9 offset:-2048 nt\n\t"
+               "global_load_dwordx4 %3, %8, %9 offset:-2032 nt\n\t"
+               "global_load_dwordx4 %4, %8, %9 offset:0 nt\n\t"
+               "global_load_dwordx4 %5, %8, %9 offset:16 nt\n\t"
+               "global_load_dwordx4 %6, %8, %9 offset:2048 nt\n\t"
+               "global_load_dwordx4 %7, %8, %9 offset:2064 nt\n\t"
+               "s_waitcnt vmcnt(0)"
+               : "=&v"(x[0]), "=&v"(y[0]), "=&v"(x[1]), "=&v"(y[1]), "=&v"(x[2]), "=&v"(y[2]), "=&v"(x[3]), "=&v"(y[3])
+               : "v"(voff), "s"(sbase)
+               : "memory");
+}
+// The product's shape (fnv_fixed32_quad_kernel): one-wave blocks of 256 keys, four key rows
+// per lane from a wave-uniform base, nt loads and stores; the memory floor of that shape
+// (k_mem_quad) and the shipped four-key statement itself (k_full_quad).  n % 256 == 0 here.
+__global__ __launch_bounds__(64) void k_mem_quad(const uint4* __restrict__ keys, uint64_t n, uint64_t* __restrict__ h1) {
+  uint64_t* hb = h1 + (uint64_t)blockIdx.x * 256u;
+  const uint32_t t = threadIdx.x;
+  v4u_q x[4], y[4];
+  load_quad(reinterpret_cast<const uint8_t*>(keys + (uint64_t)blockIdx.x * 512u) + 4096, t * 32u, x, y);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    __builtin_nontemporal_store(((uint64_t)(x[j].x ^ x[j].z ^ y[j].x ^ y[j].z) << 32) | (x[j].y ^ x[j].w ^ y[j].y ^ y[j].w),
+                                &hb[64 * j + t]);
+}
+__global__ __launch_bounds__(64) void k_full_quad(const uint4* __restrict__ keys, uint64_t n, uint64_t seed, uint64_t* __restrict__ h1) {
+  const uint64_t first = (uint64_t)blockIdx.x * 256u;
+  fnv_key32_quad_x<4>(threadIdx.x * 32u, (const uint8_t*)(keys + 2 * first) + 4096, threadIdx.x * 8u, h1 + first, seed);
+}
 
 int main() {
   const uint64_t n = 1ull << 24;
@@ -57,10 +91,12 @@ int main() {
   CHK(hipMemset(k0, 0x5a, n * 32)); CHK(hipMemset(k1, 0xa5, n * 32));
   hipEvent_t e0, e1; CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
   const unsigned g = (unsigned)(n / 256);
-  const char* names[] = {"memory floor (load 32B, store 8B)", "read-only floor (load 32B)", "VALU floor (no loads)", "full fixed32 (flat)"};
-  std::vector<float> t[4];
+  const char* names[] = {"memory floor (load 32B, store 8B)", "read-only floor (load 32B)", "VALU floor (no loads)", "full fixed32 (flat)",
+                         "memory floor, quad shape (nt, 64-thr)", "full fixed32, quad statement"};
+  const int NV = 6;
+  std::vector<float> t[NV];
   for (int r = 0; r < 7; ++r) {
-    for (int v = 0; v < 4; ++v) {
+    for (int v = 0; v < NV; ++v) {
       const int reps = 10;
       CHK(hipEventRecord(e0));
       for (int i = 0; i < reps; ++i) {
@@ -68,14 +104,16 @@ int main() {
         if (v == 0) k_mem<<<g, 256>>>(k, n, h);
         else if (v == 1) k_read<<<g, 256>>>(k, n, h);
         else if (v == 2) k_alu<<<g, 256>>>(n, 14695981039346656037ULL, h, clk);
-        else k_full<<<g, 256>>>(k, n, 14695981039346656037ULL, h);
+        else if (v == 3) k_full<<<g, 256>>>(k, n, 14695981039346656037ULL, h);
+        else if (v == 4) k_mem_quad<<<g, 64>>>(k, n, h);
+        else k_full_quad<<<g, 64>>>(k, n, 14695981039346656037ULL, h);
       }
       CHK(hipEventRecord(e1)); CHK(hipEventSynchronize(e1));
       float ms; CHK(hipEventElapsedTime(&ms, e0, e1));
       t[v].push_back(ms / reps);
     }
   }
-  for (int v = 0; v < 4; ++v) {
+  for (int v = 0; v < NV; ++v) {
     std::sort(t[v].begin(), t[v].end());
     double med = t[v][t[v].size() / 2];
     printf("%-40s median %8.2f us  min %8.2f us  -> %7.1f GB/s at 40 B/key (%.1f%% of 8 TB/s)\n", names[v], med * 1e3,

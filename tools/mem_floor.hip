@@ -46,6 +46,37 @@ __global__ __launch_bounds__(256) void k(const uint4* __restrict__ keys, uint64_
   }
 }
 
+// Eight nt loads of a wave's four key rows, each a wave-uniform base + 32-bit lane offset +
+// immediate (the base biased by 4 KiB so that the 13-bit signed immediate reaches every row).
+typedef uint32_t v4u_q __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void load_quad(const void* sbase, uint32_t voff, v4u_q (&x)[4], v4u_q (&y)[4]) {
+  asm volatile("global_load_dwordx4 %0, %8, %9 offset:-4096 nt\n\t"
+               "global_load_dwordx4 %1, %8, %9 offset:-4080 nt\n\t"
+               "global_load_dwordx4 %2, %8, %9 offset:-2048 nt\n\t"
+               "global_load_dwordx4 %3, %8, %9 offset:-2032 nt\n\t"
+               "global_load_dwordx4 %4, %8, %9 offset:0 nt\n\t"
+               "global_load_dwordx4 %5, %8, %9 offset:16 nt\n\t"
+               "global_load_dwordx4 %6, %8, %9 offset:2048 nt\n\t"
+               "global_load_dwordx4 %7, %8, %9 offset:2064 nt\n\t"
+               "s_waitcnt vmcnt(0)"
+               : "=&v"(x[0]), "=&v"(y[0]), "=&v"(x[1]), "=&v"(y[1]), "=&v"(x[2]), "=&v"(y[2]), "=&v"(x[3]), "=&v"(y[3])
+               : "v"(voff), "s"(sbase)
+               : "memory");
+}
+// The product's fixed32 access shape (fnv_fixed32_quad_kernel): one-wave blocks of 256 keys,
+// four key rows per lane, every access a wave-uniform base + 32-bit lane offset + immediate,
+// all eight nt loads issued before the first use, four nt stores at the end.
+__global__ __launch_bounds__(64) void k_quad(const uint4* __restrict__ keys, uint64_t n, uint64_t* __restrict__ h1) {
+  uint64_t* hb = h1 + (uint64_t)blockIdx.x * 256u;
+  const uint32_t t = threadIdx.x;
+  v4u_q x[4], y[4];
+  load_quad(reinterpret_cast<const uint8_t*>(keys + (uint64_t)blockIdx.x * 512u) + 4096, t * 32u, x, y);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    __builtin_nontemporal_store(mix(make_uint4(x[j].x, x[j].y, x[j].z, x[j].w), make_uint4(y[j].x, y[j].y, y[j].z, y[j].w)),
+                                &hb[64 * j + t]);
+}
+
 int main() {
   const uint64_t n = 1ull << 24;
   uint4 *k0, *k1; uint64_t *h;
@@ -54,8 +85,8 @@ int main() {
   hipEvent_t e0, e1; CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
   const unsigned g = (unsigned)(n / 256);
   const char* names[] = {"ld 2x16B, st 8B", "ld nt, st 8B", "ld, st nt", "ld nt, st nt", "ld, st paired 16B",
-                         "ld coalesced+LDS, st 8B", "ld coalesced+LDS, st nt"};
-  const int NV = 7;
+                         "ld coalesced+LDS, st 8B", "ld coalesced+LDS, st nt", "quad: sgpr base, 4 rows, nt, 64-thr"};
+  const int NV = 8;
   std::vector<float> t[NV];
   for (int r = 0; r < 7; ++r)
     for (int v = 0; v < NV; ++v) {
@@ -71,6 +102,7 @@ int main() {
           case 4: k<4><<<g, 256>>>(kk, n, h); break;
           case 5: k<5><<<g, 256>>>(kk, n, h); break;
           case 6: k<6><<<g, 256>>>(kk, n, h); break;
+          case 7: k_quad<<<g, 64>>>(kk, n, h); break;
         }
       }
       CHK(hipEventRecord(e1)); CHK(hipEventSynchronize(e1));
