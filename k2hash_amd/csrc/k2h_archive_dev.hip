@@ -27,7 +27,7 @@
 #include <mutex>
 
 #include "../../include/k2hash_amd.h"
-#include "k2h_fnv_device.h"
+#include "k2h_endwalk.h"
 #include "k2h_kernels.h"
 
 namespace k2h {
@@ -48,7 +48,6 @@ constexpr uint32_t kEnd = 0xFFFFFFFFu;   // the scan stops after this record
 constexpr uint32_t kMiss = 0xFFFFFFFEu;  // a header fits at the next offset, but it is no candidate
 constexpr uint64_t kMaxCand = 0xFFFFFFFEull;  // candidate indices are 32-bit: more is K2H_AMD_EINVAL
 
-typedef uint32_t u32x4_ua __attribute__((ext_vector_type(4), aligned(1)));
 typedef uint64_t u64_ua __attribute__((aligned(1)));
 typedef uint32_t u32_ua __attribute__((aligned(1)));
 
@@ -84,8 +83,6 @@ struct FileView {
   }
 };
 
-__device__ inline uint64_t pack64(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
-
 // ---------------------------------------------------------------------------
 // Detect.
 // ---------------------------------------------------------------------------
@@ -116,7 +113,7 @@ __device__ inline uint32_t piece_mask(uint4 v, uint32_t halo) {
     const uint32_t j = t & 7u, b = t >> 3;
     const uint32_t lo = j == 0 ? w0 : j == 1 ? w1 : j == 2 ? w2 : w3;
     const uint32_t hi = j == 0 ? w1 : j == 1 ? w2 : j == 2 ? w3 : w4;
-    const uint64_t x = ((((uint64_t)hi << 32) | lo) >> (8 * b)) & 0xFFFFFFFFFFull;
+    const uint64_t x = (pack2(lo, hi) >> (8 * b)) & 0xFFFFFFFFFFull;
     m |= x == kMagic5 ? 1u << (4 * j + b) : 0u;
   }
   return m;
@@ -174,7 +171,7 @@ __device__ inline uint64_t next_offset(const FileView& fv, uint64_t off) {
   // record apart from its neighbours': each one costs the wave 64 lines, whatever its width)
   const uint64_t l0 = fv.ld8(off + 24);
   const uint4 a = fv.ld16(off + 32), b = fv.ld16(off + 48);
-  const uint64_t len[5] = {l0, pack64(a.x, a.y), pack64(a.z, a.w), pack64(b.x, b.y), pack64(b.z, b.w)};
+  const uint64_t len[5] = {l0, pack2(a.x, a.y), pack2(a.z, a.w), pack2(b.x, b.y), pack2(b.z, b.w)};
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
     if (total + len[j] < total) overflow = true;
@@ -250,10 +247,10 @@ __device__ inline Header read_header(const FileView& fv, uint64_t off) {
   // bytes [16, 104) of the header in six loads, not eleven (see next_offset)
   const uint4 a = fv.ld16(off + 16), b = fv.ld16(off + 32), c = fv.ld16(off + 48), d = fv.ld16(off + 64),
               e = fv.ld16(off + 80);
-  h.r.type = (int64_t)pack64(a.x, a.y);
-  len[0] = pack64(a.z, a.w), len[1] = pack64(b.x, b.y), len[2] = pack64(b.z, b.w);
-  len[3] = pack64(c.x, c.y), len[4] = pack64(c.z, c.w);
-  pos[0] = pack64(d.x, d.y), pos[1] = pack64(d.z, d.w), pos[2] = pack64(e.x, e.y), pos[3] = pack64(e.z, e.w);
+  h.r.type = (int64_t)pack2(a.x, a.y);
+  len[0] = pack2(a.z, a.w), len[1] = pack2(b.x, b.y), len[2] = pack2(b.z, b.w);
+  len[3] = pack2(c.x, c.y), len[4] = pack2(c.z, c.w);
+  pos[0] = pack2(d.x, d.y), pos[1] = pack2(d.z, d.w), pos[2] = pack2(e.x, e.y), pos[3] = pack2(e.z, e.w);
   pos[4] = fv.ld8(off + 96);
   h.r.offset = off;
   int32_t status = (h.r.type < 0 || h.r.type > 6) ? K2H_AMD_ARCHIVE_BAD_TYPE : 0;
@@ -347,28 +344,12 @@ __device__ inline void hash_raw_checked(const FileView& fv, uint64_t off, uint64
   if (!fv.has(off, len) || len == 0) return;
   const uint64_t k = (len + 15) / 16;
   const uint32_t p = (uint32_t)(16 * k - len);
-  uint4 c;
-  if (off >= p) {
-    c = fv.ld16(off - p);
-  } else {  // the key starts within 15 bytes of the file's start: nothing before it to read
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (uint32_t j = 0; j < 16; ++j) w[j >> 2] |= (j >= p ? fv.byte(off + (j - p)) : 0u) << (8 * (j & 3));
-    c = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  const uint32_t m0 = p >= 4 ? 0u : ~0u << (8 * p), m1 = p >= 8 ? 0u : p <= 4 ? ~0u : ~0u << (8 * (p - 4));
-  const uint32_t m2 = p >= 12 ? 0u : p <= 8 ? ~0u : ~0u << (8 * (p - 8)), m3 = p <= 12 ? ~0u : ~0u << (8 * (p - 12));
-  c.x &= m0, c.y &= m1, c.z &= m2, c.w &= m3;
-  uint32_t lo = (uint32_t)sp.v[p], hi = (uint32_t)(sp.v[p] >> 32), lo2, hi2;
-  const uint64_t c0 = off - p;  // (wraps when off < p; then k == 1 ... or the chunks below start at c0 + 16 q >= off)
-  for (uint64_t q = 1; q < k; ++q) {
-    const uint4 nx = fv.ld16(c0 + 16 * q);
-    fnv_chunk16(lo, hi, c);
-    c = nx;
-  }
-  fnv_chunk16_last(lo, hi, lo2, hi2, c);
-  h1 = ((uint64_t)hi << 32) | lo;
-  h2 = len == 1 ? h1 : ((uint64_t)hi2 << 32) | lo2;  // lib/k2hashfunc.cc:83
+  // (a key that starts within 15 bytes of the file's start has nothing before it to read)
+  const uint4 c0 =
+      off >= p ? fv.ld16(off - p) : chunk0_from_bytes(p, [fv, off](uint32_t i) { return fv.byte(off + i); });
+  const uint64_t at = off - p;  // (wraps when off < p; chunks q >= 1 start at at + 16 q >= off)
+  end_aligned_walk(k, p, mask_lead_sel(c0, p), sp.v, [fv, at](uint64_t q) { return fv.ld16(at + 16 * q); }, h1, h2);
+  if (len == 1) h2 = h1;  // lib/k2hashfunc.cc:83
 }
 
 struct HashOut {

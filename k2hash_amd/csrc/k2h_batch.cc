@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/k2hash_amd.h"
+#include "k2h_fnv_device.h"
 #include "k2h_kernels.h"
 
 namespace {
@@ -38,7 +39,7 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
 }
 
 uint64_t seed_for(uint32_t flags) {
-  return (flags & K2H_AMD_FLAG_STD_FNV) ? k2h::kSeedStdValue : k2h::kSeedBuiltinValue;
+  return (flags & K2H_AMD_FLAG_STD_FNV) ? k2h::kSeedStd : k2h::kSeedBuiltin;
 }
 
 // ---------------------------------------------------------------------------

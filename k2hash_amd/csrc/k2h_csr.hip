@@ -26,45 +26,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "k2h_fnv_device.h"
+#include "k2h_endwalk.h"
 #include "k2h_kernels.h"
 
 namespace k2h {
 
 namespace {
 
-typedef uint32_t u32x4_ua __attribute__((ext_vector_type(4), aligned(1)));
 typedef uint32_t u32x4_v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) const u32x4_v gvec4;
-
-__device__ __forceinline__ uint4 ld16(const uint8_t* p) {
-  u32x4_ua v = *reinterpret_cast<const u32x4_ua*>(p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// 16 bytes at p where bytes below `lo` must not be touched (they are don't-care).
-__device__ __forceinline__ uint4 ld16_lowguard(const uint8_t* p, const uint8_t* lo) {
-  if (p >= lo) return ld16(p);
-  uint32_t w[4] = {0, 0, 0, 0};
-  for (int j = 0; j < 16; ++j)
-    if (p + j >= lo) w[j >> 2] |= (uint32_t)p[j] << (8 * (j & 3));
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// Zero the first p (0..15) bytes of a chunk.
-__device__ __forceinline__ uint4 mask_lead(uint4 c, uint32_t p) {
-  // word mask = low half of (~0 << clamp(8p - base, 0, 32)): sub, med3, 64-bit shift
-  // (a 32-bit shift cannot produce the all-zero mask), no compares or selects
-  int32_t sh = (int32_t)(8u * p);
-  auto m = [sh](int32_t base) -> uint32_t {
-    int32_t t = sh - base;
-    t = t < 0 ? 0 : (t > 32 ? 32 : t);
-    return (uint32_t)(~0ull << t);
-  };
-  return make_uint4(c.x & m(0), c.y & m(32), c.z & m(64), c.w & m(96));
-}
-
-__device__ __forceinline__ uint64_t pack2(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
 
 __device__ __forceinline__ uint32_t bperm(uint32_t v, uint32_t src_lane) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v);
@@ -114,20 +84,9 @@ __device__ __forceinline__ void hash_key(const uint8_t* s, const uint8_t* e, con
     r1 = r2 = 0;
     return;
   }
-  uint64_t k = (len + 15) >> 4;
-  uint32_t p = (uint32_t)(16 * k - len);
-  const uint8_t* cp = e - 16 * k;
-  uint64_t st = spad[p];
-  uint32_t lo = (uint32_t)st, hi = (uint32_t)(st >> 32), lo2, hi2;
-  uint4 c = mask_lead(ld16_lowguard(cp, lo_bound), p);
-  for (uint64_t j = 1; j < k; ++j) {
-    uint4 nx = ld16(cp + 16 * j);
-    fnv_chunk16(lo, hi, c);
-    c = nx;
-  }
-  fnv_chunk16_last(lo, hi, lo2, hi2, c);
-  r1 = pack2(lo, hi);
-  r2 = len == 1 ? r1 : pack2(lo2, hi2);  // length 1: second hash not shortened (lib/k2hashfunc.cc:83)
+  const uint64_t k = (len + 15) >> 4;
+  end_aligned_walk_ptr(k, (uint32_t)(16 * k - len), e - 16 * k, lo_bound, spad, r1, r2);
+  if (len == 1) r2 = r1;  // length 1: second hash not shortened (lib/k2hashfunc.cc:83)
 }
 
 
@@ -255,16 +214,10 @@ __device__ __forceinline__ uint32_t len_bin128_32(uint32_t len) {
 // The reference's second hash from the first and the key's last byte: h1 = (h2 ^
 // sext(b)) * P (lib/k2hashfunc.cc:53-56), P odd, so h2 = (h1 * P^-1) ^ sext(b); for a
 // one-byte key h2 = h1 (lib/k2hashfunc.cc:83), for an empty one 0.
-constexpr uint64_t prime_inverse() {
-  uint64_t x = 1099511628211ULL;
-  for (int i = 0; i < 6; ++i) x *= 2 - 1099511628211ULL * x;
-  return x;
-}
-static_assert(prime_inverse() * 1099511628211ULL == 1, "P^-1 mod 2^64");
 __device__ __forceinline__ uint64_t second_from_first(uint64_t h1v, uint32_t len, const uint8_t* key_end) {
   if (len <= 1) return h1v;  // 0 for an empty key, h1 for a one-byte key
   const int64_t sb = (int64_t)(int8_t)key_end[-1];
-  return (h1v * prime_inverse()) ^ (uint64_t)sb;
+  return (h1v * kPrimeInverse) ^ (uint64_t)sb;
 }
 
 // Two keys per lane, back to back: key 0 (k0 >= 1 chunks unless the lane is idle) then
@@ -441,15 +394,7 @@ __global__ __launch_bounds__(256) void fnv_csr_staged_kernel(const uint8_t* __re
                            h2, bp);
     return;
   }
-  if (tid < 16) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {  // bytes >= p kept: chunk 0's p pad bytes zeroed
-      const int32_t sh = 8 * ((int32_t)tid - 4 * i);
-      w[i] = sh <= 0 ? ~0u : sh >= 32 ? 0u : ~0u << sh;
-    }
-    s_mask[tid] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  if (tid < 16) s_mask[tid] = mask_lead(make_uint4(~0u, ~0u, ~0u, ~0u), tid);  // chunk 0's p pad bytes zeroed
   {  // a thread's three offset loads in flight together (a loop waited for each in turn:
      // round-3 lab A/B, -2 % on config 3, profiles/r03r_csr_ab.json)
     uint32_t r[3];
@@ -548,11 +493,11 @@ __global__ __launch_bounds__(256) void fnv_csr_staged_kernel(const uint8_t* __re
 // Fixed-length keys other than the 32-byte fast path (e.g. BASELINE config 5,
 // 4 KiB): one lane per key, the same chunk walker, uniform trip count.
 // ---------------------------------------------------------------------------
-template <bool H2, bool DIRECT, bool EPI = false>
+template <bool H2, bool DIRECT, bool EPI>
 __global__ __launch_bounds__(256) void fnv_fixed_long_kernel(const uint8_t* __restrict__ base, uint64_t key_len,
                                                              uint64_t n, SpadTable spad_tab,
                                                              uint64_t* __restrict__ h1, uint64_t* __restrict__ h2,
-                                                             BucketParams bp = {}) {
+                                                             BucketParams bp) {
   __shared__ uint64_t s_spad[16];
   __shared__ Ring s_ring[DIRECT ? 1 : 4];
   if (threadIdx.x < 16) s_spad[threadIdx.x] = spad_tab.v[threadIdx.x];
@@ -602,10 +547,10 @@ __global__ __launch_bounds__(256) void fnv_fixed_long_kernel(const uint8_t* __re
 // The hash stores come after the loop.  tests/test_kernel_source.py checks the loop body
 // for stores.
 // ---------------------------------------------------------------------------
-template <bool H2, bool EPI = false>
+template <bool H2, bool EPI>
 __global__ __launch_bounds__(64) void fnv_fixed_lines_kernel(const uint8_t* __restrict__ base, uint64_t key_len,
                                                              uint64_t n, uint64_t seed, uint64_t* __restrict__ h1,
-                                                             uint64_t* __restrict__ h2, BucketParams bp = {}) {
+                                                             uint64_t* __restrict__ h2, BucketParams bp) {
   constexpr uint32_t RB = 128, NP = 8, SLOT = 64 * RB;
   __shared__ __attribute__((aligned(1024))) uint8_t ring[2 * SLOT];
   const uint32_t t = threadIdx.x;
@@ -669,16 +614,13 @@ __global__ __launch_bounds__(64) void fnv_fixed_lines_kernel(const uint8_t* __re
   if constexpr (EPI) bucket_emit(bp, i, r1);
 }
 
-// S_p = seed * P^-p mod 2^64, p = 0..15 (P = 1099511628211 is odd, so invertible).
+// S_p = seed * P^-p mod 2^64, p = 0..15.
 SpadTable make_spad(uint64_t seed) {
-  const uint64_t P = 1099511628211ULL;
-  uint64_t inv = P;  // Newton: inv = inv * (2 - P*inv); P*P = 1 mod 8, 5 doublings reach 64 bits
-  for (int i = 0; i < 6; ++i) inv *= 2 - P * inv;
   SpadTable t;
   uint64_t s = seed;
   for (int p = 0; p < 16; ++p) {
     t.v[p] = s;
-    s *= inv;
+    s *= kPrimeInverse;
   }
   return t;
 }
@@ -688,14 +630,10 @@ hipError_t launch_csr_tile(const void* bytes, const uint64_t* offsets, uint64_t 
   const SpadTable t = make_spad(seed);
   const unsigned g = (unsigned)((n + kTileKeys - 1) / kTileKeys);
   const uint8_t* b = (const uint8_t*)bytes;
-  const BucketParams none{};
-  if (bp) {
-    if (h2) fnv_csr_staged_kernel<true, true><<<g, 256, 0, stream>>>(b, offsets, n, t, h1, h2, *bp);
-    else fnv_csr_staged_kernel<false, true><<<g, 256, 0, stream>>>(b, offsets, n, t, h1, nullptr, *bp);
-  } else {
-    if (h2) fnv_csr_staged_kernel<true, false><<<g, 256, 0, stream>>>(b, offsets, n, t, h1, h2, none);
-    else fnv_csr_staged_kernel<false, false><<<g, 256, 0, stream>>>(b, offsets, n, t, h1, nullptr, none);
-  }
+  const BucketParams p = bp ? *bp : BucketParams{};
+  with_h2_epi(h2, bp, [&](auto H2, auto EPI) {
+    fnv_csr_staged_kernel<H2.value, EPI.value><<<g, 256, 0, stream>>>(b, offsets, n, t, h1, h2, p);
+  });
   return hipGetLastError();
 }
 
@@ -709,38 +647,20 @@ bool fixed_lines_ok(const void* keys, uint64_t key_len) {
 hipError_t launch_fixed_long(const void* keys, uint64_t key_len, uint64_t n, uint64_t seed, uint64_t* h1,
                              uint64_t* h2, hipStream_t stream, const BucketParams* bp) {
   const uint8_t* k = (const uint8_t*)keys;
-  if (fixed_lines_ok(keys, key_len)) {  // 2 rounds of whole 128-byte lines per lane in the LDS ring
-    const unsigned g = (unsigned)((n + 63) / 64);
-    if (bp) {
-      if (h2) fnv_fixed_lines_kernel<true, true><<<g, 64, 0, stream>>>(k, key_len, n, seed, h1, h2, *bp);
-      else fnv_fixed_lines_kernel<false, true><<<g, 64, 0, stream>>>(k, key_len, n, seed, h1, nullptr, *bp);
-    } else {
-      if (h2) fnv_fixed_lines_kernel<true><<<g, 64, 0, stream>>>(k, key_len, n, seed, h1, h2);
-      else fnv_fixed_lines_kernel<false><<<g, 64, 0, stream>>>(k, key_len, n, seed, h1, nullptr);
+  const BucketParams p = bp ? *bp : BucketParams{};
+  with_h2_epi(h2, bp, [&](auto H2, auto EPI) {
+    if (fixed_lines_ok(keys, key_len)) {  // 2 rounds of whole 128-byte lines per lane in the LDS ring
+      fnv_fixed_lines_kernel<H2.value, EPI.value>
+          <<<(unsigned)((n + 63) / 64), 64, 0, stream>>>(k, key_len, n, seed, h1, h2, p);
+      return;
     }
-    return hipGetLastError();
-  }
-  const SpadTable t = make_spad(seed);
-  const unsigned g = (unsigned)((n + 255) / 256);
-  const BucketParams none{};
-  const BucketParams& p = bp ? *bp : none;
-  if (key_len < 128) {  // per-lane direct loads
-    if (bp) {
-      if (h2) fnv_fixed_long_kernel<true, true, true><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, h2, p);
-      else fnv_fixed_long_kernel<false, true, true><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, nullptr, p);
-    } else {
-      if (h2) fnv_fixed_long_kernel<true, true><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, h2);
-      else fnv_fixed_long_kernel<false, true><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, nullptr);
-    }
-  } else {  // the cooperative line ring
-    if (bp) {
-      if (h2) fnv_fixed_long_kernel<true, false, true><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, h2, p);
-      else fnv_fixed_long_kernel<false, false, true><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, nullptr, p);
-    } else {
-      if (h2) fnv_fixed_long_kernel<true, false><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, h2);
-      else fnv_fixed_long_kernel<false, false><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, nullptr);
-    }
-  }
+    const SpadTable t = make_spad(seed);
+    const unsigned g = (unsigned)((n + 255) / 256);
+    if (key_len < 128)  // per-lane direct loads
+      fnv_fixed_long_kernel<H2.value, true, EPI.value><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, h2, p);
+    else  // the cooperative line ring
+      fnv_fixed_long_kernel<H2.value, false, EPI.value><<<g, 256, 0, stream>>>(k, key_len, n, t, h1, h2, p);
+  });
   return hipGetLastError();
 }
 

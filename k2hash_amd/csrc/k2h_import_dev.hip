@@ -22,7 +22,7 @@
 #include <mutex>
 
 #include "../../include/k2hash_amd.h"
-#include "k2h_fnv_device.h"
+#include "k2h_endwalk.h"
 #include "k2h_kernels.h"
 
 namespace k2h {
@@ -38,12 +38,6 @@ constexpr int kThreads = 256;
 // key (lib/k2hshm.cc:2081-2083): a zero byte is a bare multiply, so h1 = state * P and
 // h2 = state (lib/k2hashfunc.cc:83-85); the empty key is the one-byte "\0", h1 = h2 =
 // seed * P.
-typedef uint32_t u32x4_ua __attribute__((ext_vector_type(4), aligned(1)));
-
-__device__ inline uint4 ld16(const uint8_t* p) {
-  const u32x4_ua v = *reinterpret_cast<const u32x4_ua*>(p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
 
 // The key [off, off + len) + NUL.  Callers go through hash_cstr_checked below, never this.
 __device__ inline void hash_cstr_unchecked(const uint8_t* __restrict__ f, uint64_t off, uint64_t len,
@@ -53,18 +47,9 @@ __device__ inline void hash_cstr_unchecked(const uint8_t* __restrict__ f, uint64
     const uint64_t k = (len + 15) / 16;
     const uint32_t p = (uint32_t)(16 * k - len);
     const uint8_t* c0 = f + off - p;  // chunk 0 (its first p bytes are not the key's)
-    uint4 c;
-    if (off >= p) {
-      c = ld16(c0);
-    } else {  // the key starts the file: no bytes before it to over-read
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t j = p; j < 16; ++j) w[j >> 2] |= (uint32_t)f[off - p + j] << (8 * (j & 3));
-      c = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    // zero bytes [0, p)
-    const uint32_t m0 = p >= 4 ? 0u : ~0u << (8 * p), m1 = p >= 8 ? 0u : p <= 4 ? ~0u : ~0u << (8 * (p - 4));
-    const uint32_t m2 = p >= 12 ? 0u : p <= 8 ? ~0u : ~0u << (8 * (p - 8)), m3 = p <= 12 ? ~0u : ~0u << (8 * (p - 12));
-    c.x &= m0, c.y &= m1, c.z &= m2, c.w &= m3;
+    // (a key that starts the file has no bytes before it to over-read)
+    uint4 c = off >= p ? ld16(c0) : chunk0_from_bytes(p, [=](uint32_t i) { return (uint32_t)c0[p + i]; });
+    c = mask_lead_sel(c, p);
     uint32_t lo = (uint32_t)sp.v[p], hi = (uint32_t)(sp.v[p] >> 32);
     // chunks 1-3 loaded before any is hashed, later ones one ahead (round 5: one load per
     // loop trip, each waited for in turn, cost the miss-heavy mdbm pass B a round trip per chunk)
@@ -84,9 +69,9 @@ __device__ inline void hash_cstr_unchecked(const uint8_t* __restrict__ f, uint64
       }
       fnv_chunk16(lo, hi, nx);
     }
-    raw = ((uint64_t)hi << 32) | lo;
+    raw = pack2(lo, hi);
   }
-  h1 = raw * 1099511628211ULL;  // lib/k2hashfunc.cc:56
+  h1 = raw * kPrime;  // lib/k2hashfunc.cc:56
   h2 = len ? raw : h1;
 }
 
@@ -535,18 +520,9 @@ __device__ inline uint64_t key_raw_lds(const uint8_t* lds_key, uint32_t len, con
   if (!len) return sp.v[0];
   const uint32_t k = (len + 15) / 16, p = 16 * k - len;
   const uint8_t* c0 = lds_key - p;
-  uint4 c = ld16(c0);
-  const uint32_t m0 = p >= 4 ? 0u : ~0u << (8 * p), m1 = p >= 8 ? 0u : p <= 4 ? ~0u : ~0u << (8 * (p - 4));
-  const uint32_t m2 = p >= 12 ? 0u : p <= 8 ? ~0u : ~0u << (8 * (p - 8)), m3 = p <= 12 ? ~0u : ~0u << (8 * (p - 12));
-  c.x &= m0, c.y &= m1, c.z &= m2, c.w &= m3;
-  uint32_t lo = (uint32_t)sp.v[p], hi = (uint32_t)(sp.v[p] >> 32);
-  for (uint32_t q = 1; q < k; ++q) {
-    const uint4 nx = ld16(c0 + 16 * q);
-    fnv_chunk16(lo, hi, c);
-    c = nx;
-  }
-  fnv_chunk16(lo, hi, c);
-  return ((uint64_t)hi << 32) | lo;
+  uint64_t raw, unused;
+  end_aligned_walk<false>(k, p, mask_lead_sel(ld16(c0), p), sp.v, [=](uint32_t q) { return ld16(c0 + 16 * q); }, raw, unused);
+  return raw;
 }
 
 // Speculative keys: pass A does not know the mode at its block's start, but a key starts
@@ -1127,7 +1103,7 @@ __global__ __launch_bounds__(64) void tsv_b_kernel(const uint8_t* __restrict__ f
         uint64_t a, c;
         if (hit) {
           const uint64_t raw = s_slot[3 * threadIdx.x + j];
-          a = raw * 1099511628211ULL;  // the NUL: a bare multiply (lib/k2hashfunc.cc:56)
+          a = raw * kPrime;  // the NUL: a bare multiply (lib/k2hashfunc.cc:56)
           c = len ? raw : a;
         } else {  // a state outside the file (never for correct states): wrong records, not a fault
           hash_cstr_checked(f, size, s.fs, len, sp, a, c);
@@ -1243,7 +1219,7 @@ __global__ __launch_bounds__(64) void tsv_b_kernel(const uint8_t* __restrict__ f
         hash_cstr_checked(f, size, s_rec[4 * x], s_rec[4 * x + 1], sp, a, c);  // (a wrong state: wrong records, no fault)
       } else {
         const uint64_t raw = s_slot[code - 1];
-        a = raw * 1099511628211ULL;  // the NUL: a bare multiply (lib/k2hashfunc.cc:56)
+        a = raw * kPrime;  // the NUL: a bare multiply (lib/k2hashfunc.cc:56)
         c = s_rec[4 * x + 1] ? raw : a;
       }
       __builtin_nontemporal_store(a, h1 + su.r + x - HDR);

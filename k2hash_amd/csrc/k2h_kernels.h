@@ -4,12 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/k2hash_amd.h"
 
 namespace k2h {
-
-constexpr uint64_t kSeedBuiltinValue = 14695981039346656037ULL;  // lib/k2hashfunc.cc:51
-constexpr uint64_t kSeedStdValue = 2166136261ULL;                  // libstdc++ _Fnv_hash_impl seed
 
 // Bucket-index epilogue: where a hash lands in a k2hash table with
 // masks (cur_mask, collision_mask) -- the stateless part of K2HShm::GetKIndexPos
@@ -78,6 +77,19 @@ __device__ __forceinline__ void bucket_emit(const BucketParams& bp, uint64_t i, 
   }
 }
 #endif
+
+// The launch ladder: the runtime pair (second hash wanted, index epilogue wanted) as the
+// kernels' two template booleans.  f is a generic lambda taking two std::bool_constant values.
+template <class F>
+inline void with_h2_epi(bool h2, bool epi, F&& f) {
+  if (epi) {
+    if (h2) f(std::true_type{}, std::true_type{});
+    else f(std::false_type{}, std::true_type{});
+  } else {
+    if (h2) f(std::true_type{}, std::false_type{});
+    else f(std::false_type{}, std::false_type{});
+  }
+}
 
 // Standalone epilogue over hashes already in device memory.
 hipError_t launch_bucket_index(const uint64_t* h1, uint64_t n, const BucketParams& bp, hipStream_t stream);

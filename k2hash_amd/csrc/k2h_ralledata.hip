@@ -23,14 +23,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "k2h_fnv_device.h"
+#include "k2h_endwalk.h"
 #include "k2h_kernels.h"
 
 namespace k2h {
 namespace {
-
-typedef uint64_t u64_ua __attribute__((aligned(1)));
-typedef uint32_t u32x4_ua __attribute__((ext_vector_type(4), aligned(1)));
 
 // Workgroup barrier over LDS only (see its use in ralledata_gather_kernel).
 __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -88,22 +85,11 @@ constexpr int kGatherPieces = (80 * kGatherRecs + kGatherPool) / 16 + 2;
 // chunks; bytes below the key buffer are never read.
 __device__ __forceinline__ void global_key_hash(const uint8_t* keys, uint64_t b, uint64_t e, const uint64_t* spad,
                                                 uint64_t& r1, uint64_t& r2) {
+  r1 = r2 = 0;  // empty key (lib/k2hashfunc.cc:66-68, 80-82)
+  if (e == b) return;
   const uint64_t len = e - b, k = (len + 15) >> 4;
-  const uint32_t p = (uint32_t)(16 * k - len);
-  const uint8_t* cp = keys + e - 16 * k;
-  const uint64_t st = spad[p & 15];
-  uint32_t lo = (uint32_t)st, hi = (uint32_t)(st >> 32), lo2 = lo, hi2 = hi;
-  uint32_t w[4] = {0, 0, 0, 0};
-  for (uint32_t j = p; j < 16 && k; ++j) w[j >> 2] |= (uint32_t)cp[j] << (8 * (j & 3));
-  uint4 c = make_uint4(w[0], w[1], w[2], w[3]);
-  for (uint64_t j = 1; j < k; ++j) {
-    fnv_chunk16(lo, hi, c);
-    const u32x4_ua v = *reinterpret_cast<const u32x4_ua*>(cp + 16 * j);
-    c = make_uint4(v.x, v.y, v.z, v.w);
-  }
-  fnv_chunk16_last(lo, hi, lo2, hi2, c);
-  r1 = k ? ((uint64_t)hi << 32) | lo : 0;
-  r2 = k ? (len == 1 ? r1 : ((uint64_t)hi2 << 32) | lo2) : 0;
+  end_aligned_walk_ptr<true, false>(k, (uint32_t)(16 * k - len), keys + e - 16 * k, keys, spad, r1, r2);
+  if (len == 1) r2 = r1;  // lib/k2hashfunc.cc:83
 }
 
 // one record by a group of G lanes, straight to HBM (the group form); lane 0 hashes the key
@@ -145,22 +131,17 @@ __device__ __forceinline__ void group_record(const RalleInputs& in, uint64_t n, 
 // byte 15 step leaves the second hash (the state before the last byte).
 __device__ __forceinline__ void staged_key_hash(const uint8_t* end, uint32_t len, const uint64_t* spad, uint64_t& r1,
                                                 uint64_t& r2) {
-  const uint32_t k = (len + 15) >> 4, p = 16 * k - len;
+  // (the staged keys lie above the image's headers: chunk 0 never starts below the image.  An
+  // empty key is passed to the walk as k = 0, outside its k >= 1 contract on purpose: its loop
+  // then does not run and it hashes the one chunk at `end` -- don't-care bytes, the image ends
+  // in 16 spare ones -- whose result is dropped below: no branch in wave 0's path)
+  const uint32_t k = (len + 15) >> 4;
   const uint8_t* cp = end - 16 * k;
-  const uint64_t st = spad[p & 15];
-  uint32_t lo = (uint32_t)st, hi = (uint32_t)(st >> 32), lo2 = lo, hi2 = hi;
-  u32x4_ua w = *reinterpret_cast<const u32x4_ua*>(cp);
-  const int32_t sh = (int32_t)(8 * p);
-  auto lead = [sh](int32_t b) -> uint32_t { return (uint32_t)(~0ull << min(max(sh - b, 0), 32)); };
-  uint4 c = make_uint4(w.x & lead(0), w.y & lead(32), w.z & lead(64), w.w & lead(96));
-  for (uint32_t j = 1; j < k; ++j) {
-    fnv_chunk16(lo, hi, c);
-    w = *reinterpret_cast<const u32x4_ua*>(cp + 16 * j);
-    c = make_uint4(w.x, w.y, w.z, w.w);
-  }
-  fnv_chunk16_last(lo, hi, lo2, hi2, c);
-  r1 = k ? ((uint64_t)hi << 32) | lo : 0;  // empty key hashes to 0 (lib/k2hashfunc.cc:66-68, 80-82)
-  r2 = k ? (len == 1 ? r1 : ((uint64_t)hi2 << 32) | lo2) : 0;
+  const uint32_t p = 16 * k - len;
+  end_aligned_walk<true, false>(
+      k, p, mask_lead(ld16(cp), p), spad, [=](uint32_t q) { return ld16(cp + 16 * q); }, r1, r2);
+  if (len == 1) r2 = r1;  // lib/k2hashfunc.cc:83
+  if (!len) r1 = r2 = 0;  // lib/k2hashfunc.cc:66-68, 80-82
 }
 
 // The key hashes are computed here from the staged keys (no hash kernel, no scratch).

@@ -17,12 +17,12 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "k2h_fnv_device.h"
 #include "k2h_kernels.h"
 
 namespace k2h {
 namespace {
 
-typedef uint32_t u32x4_ua __attribute__((ext_vector_type(4), aligned(1)));
 constexpr int kGroup = 16;
 
 __global__ __launch_bounds__(256) void gather_ranges_kernel(const uint8_t* __restrict__ base,
@@ -48,9 +48,8 @@ __global__ __launch_bounds__(256) void cstr_fixup_kernel(const uint64_t* __restr
                                                          uint64_t* __restrict__ h1, uint64_t* __restrict__ h2) {
   const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
-  const uint64_t P = 1099511628211ULL;  // lib/k2hashfunc.cc:56
   uint64_t raw = h1[i];
-  uint64_t a = lens[i] ? raw * P : seed * P, b = lens[i] ? raw : seed * P;
+  uint64_t a = lens[i] ? raw * kPrime : seed * kPrime, b = lens[i] ? raw : seed * kPrime;
   h1[i] = a;
   if (h2) h2[i] = b;
 }

@@ -25,8 +25,9 @@ from k2hash_amd import archive  # noqa: E402
 HBM_PEAK = 8.0e12  # bytes per second, the MI355X's specification
 
 
-def replicate(n: int, seed: int) -> np.ndarray:
-    """n records drawn from the golden file's 64, appended as K2HArchive::Save appends."""
+def replicate(n: int, seed: int, with_pick: bool = False):
+    """n records drawn from the golden file's 64, appended as K2HArchive::Save appends; with_pick:
+    also which golden record each one is."""
     f = np.frombuffer((ROOT / "tests" / "golden" / "archive.k2har").read_bytes(), np.uint8)
     recs = archive.scan(f)
     start = recs["offset"].astype(np.int64)
@@ -42,7 +43,7 @@ def replicate(n: int, seed: int) -> np.ndarray:
         src = np.repeat(start[p] - rel[:-1], lens) + np.arange(int(rel[-1]), dtype=np.int64)
         out[at:at + src.size] = f[src]
         at += src.size
-    return out
+    return (out, pick) if with_pick else out
 
 
 def median(xs):

@@ -7,9 +7,10 @@
 With --mdbm: the same records in mdbm's print format (built on the device, records checked
 against the generator and hashes against the ranges path), timed per call.
 
-With --ab LIB: same-process A/B of the working tree's library against another build of it
-(tools/build_ab.sh), interleaved rounds, each library's result checked against
-tests/golden/import_digest.json first.
+With --ab LIB[,LIB...]: same-process A/B of the working tree's library against other builds of
+it (tools/build_ab.sh), interleaved rounds, each library's result checked first (TSV: against
+tests/golden/import_digest.json; with --mdbm: as above).  List a build twice under two paths
+for the run's A/A difference.
 """
 import argparse
 import ctypes
@@ -63,51 +64,58 @@ def main():
     dev = torch.device("cuda", 0)
     if a.lib:
         _native._batch = _native._bind(ctypes.CDLL(str(Path(a.lib).resolve())), _native.SIGNATURES.keys())
-    if a.mdbm:  # one verified call, then the timed calls
+    if a.mdbm:
         data, exp = mdbm_workload(dev)
-        ok = verify_mdbm(archive.import_scan_prehash_device(data, "mdbm"), data, exp)
-        print(json.dumps({"mdbm_bytes": data.numel(), "records": int(exp.shape[0]), "verify_ok": ok}), flush=True)
-        if not ok and not a.no_parity:
-            sys.exit(1)
-        t0 = time.perf_counter()
-        while time.perf_counter() - t0 < 0.15:
-            archive.import_scan_prehash_device(data, "mdbm")
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.rounds):
-            t0 = time.perf_counter()
-            for _ in range(a.calls):
-                archive.import_scan_prehash_device(data, "mdbm")
-            torch.cuda.synchronize()
-            ts.append((time.perf_counter() - t0) / a.calls * 1e3)
-        print(json.dumps({"mdbm_ms_per_call_median": statistics.median(ts), "min": min(ts), "all": ts}))
-        return
-    data = bench.import_workload(dev)
+        call = lambda: archive.import_scan_prehash_device(data, "mdbm")  # noqa: E731
+        verify = lambda out: verify_mdbm(out, data, exp)  # noqa: E731
+    else:
+        data = bench.import_workload(dev)
+        call = lambda: archive.import_scan_prehash_device(data)  # noqa: E731
+        verify = _verify
     if a.ab:
         libs = {"tree": _native.batch_lib()}
         for p in a.ab.split(","):
             libs[p] = _native._bind(ctypes.CDLL(str(Path(p).resolve())), _native.SIGNATURES.keys())
         for name, lib in libs.items():
             _native._batch = lib  # tool only: route archive's calls to this build
-            ok = _verify(archive.import_scan_prehash_device(data))
+            ok = verify(call())
             print(f"{name}: parity {'OK' if ok else 'MISMATCH'}", flush=True)
             if not ok and not (a.no_parity and name != "tree"):
                 sys.exit(1)
         times = {k: [] for k in libs}
-        for _ in range(a.rounds):
-            for name, lib in libs.items():
+        for r in range(a.rounds):
+            order = list(libs.items())
+            for name, lib in order[r % len(order):] + order[:r % len(order)]:  # every library in every place
                 _native._batch = lib
                 for _ in range(3):
-                    archive.import_scan_prehash_device(data)
+                    call()
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(a.calls):
-                    archive.import_scan_prehash_device(data)
+                    call()
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) / a.calls * 1e3)
         for name in libs:
-            print(json.dumps({"lib": name, "ms_per_call_median": statistics.median(times[name]),
+            print(json.dumps({"mdbm": a.mdbm, "lib": name, "ms_per_call_median": statistics.median(times[name]),
                               "ms_per_call_min": min(times[name]), "all": times[name]}), flush=True)
+        return
+    if a.mdbm:  # one verified call, then the timed calls
+        ok = verify(call())
+        print(json.dumps({"mdbm_bytes": data.numel(), "records": int(exp.shape[0]), "verify_ok": ok}), flush=True)
+        if not ok and not a.no_parity:
+            sys.exit(1)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.15:
+            call()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.rounds):
+            t0 = time.perf_counter()
+            for _ in range(a.calls):
+                call()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / a.calls * 1e3)
+        print(json.dumps({"mdbm_ms_per_call_median": statistics.median(ts), "min": min(ts), "all": ts}))
         return
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < 0.15:

@@ -5,7 +5,7 @@ extern "C" __attribute__((visibility("default"))) int k2h_lab_csr(int variant, c
                                                                   void* clk, void* stream) {
   using namespace k2h;
   hipStream_t st = (hipStream_t)stream;
-  const uint64_t seed = kSeedBuiltinValue;
+  const uint64_t seed = kSeedBuiltin;
   if (variant == 0) return (int)launch_csr_tile(bytes, offsets, n, seed, h1, nullptr, st, nullptr);
   const SpadTable t = make_spad(seed);
   const unsigned g = (unsigned)((n + kTileKeys - 1) / kTileKeys);
