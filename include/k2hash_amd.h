@@ -187,6 +187,79 @@ int k2h_amd_build_ralledata_host(const void* keys, const uint64_t* key_off, cons
                                  const void* attrs, const uint64_t* attr_off, uint64_t n, void* out,
                                  uint64_t* blob_off, uint32_t flags, int device);
 
+/* 4b. The consumer side: check, route and compact a blob stream before it is fed to
+ * k2h_set_element_by_binary (which trusts the hash fields: a wrong one plants an element
+ * no Get reaches).  Device pointers only; there is no host-pointer form.
+ *
+ * The stream: blob i = blobs[blob_off[i], blob_off[i+1]), blob_off has n+1 entries
+ * relative to `blobs`, `size` is the number of readable bytes at `blobs` -- what
+ * k2h_amd_build_ralledata writes, or a K2HBIN array laid end to end (trailing slack
+ * inside a blob is allowed).
+ *
+ * k2h_amd_ralledata_check (async on `stream`): status[i] is the first that applies of
+ *   BAD_SPAN     blob_off[i+1] < blob_off[i], or blob_off[i+1] > size, or length < 80
+ *   EMPTY        all four lengths are 0                        (lib/k2hshmdirect.cc:351)
+ *   NO_KEY       key_length == 0                               (lib/k2hshmdirect.cc:355)
+ *   BAD_RANGE    for a segment of length > 0: pos < 80 (pos is a signed off_t), or
+ *                pos + len overflows or passes the blob's end; the pos of a length-0
+ *                segment is ignored, as lib/k2hshmdirect.cc:362-364 ignores it
+ *   BAD_HASH     hash field != k2h_hash(key) under `flags` (K2H_AMD_FLAG_STD_FNV is
+ *                honoured; K2H_AMD_FLAG_CSTR returns K2H_AMD_EINVAL)
+ *   BAD_SUBHASH  subhash field != k2h_second_hash(key)
+ * else OK.  Segment order and overlap are not checked (SetElementByBinArray honours any
+ * positions).  No byte outside [0, size) is read except within the aligned 16 bytes that
+ * hold a valid byte, and nothing of a BAD_SPAN blob.  h1[i] / h2[i] (each may be NULL):
+ * the recomputed hashes for status OK, BAD_HASH and BAD_SUBHASH, else 0.
+ *
+ * With `range` (route must then be given; both NULL otherwise) route[i] is 0 unless
+ * status[i] is OK, else
+ *   bit 0: the stored hash is in the target range as K2HShm::GetElementListToBinary
+ *          selects (lib/k2hshmdirect.cc:118-131):
+ *            end = (target_hash + (target_hash_range > 0 ? target_hash_range - 1 : 0))
+ *                  % target_max_hash            (the sum wraps in 64 bits)
+ *            m = hash % target_max_hash
+ *            in  = target_hash <= end ? !(m < target_hash || end < m)
+ *                                     : !(end < m && m < target_hash)
+ *          restated verbatim, target_hash >= target_max_hash included;
+ *   bit 1: the hash is in the old range, the condition under which
+ *          lib/k2hshmdirect.cc:165-176 leaves need_check_start true: the same
+ *          arithmetic over old_hash / old_max_hash (and the same target_hash_range);
+ *          0 when old_hash == ~0 (lib/k2hshmdirect.cc:119; no modulo is taken then).
+ * target_max_hash == 0, or old_max_hash == 0 with old_hash != ~0: K2H_AMD_EINVAL.
+ * Parity with GetElementListToBinary is a restatement: libk2hash itself is not built by
+ * this project's tests (it needs libfullock).
+ *
+ * k2h_amd_ralledata_select copies every blob with keep[i] != 0 and a valid span (non-
+ * decreasing, ending at or before size) back to back, in order, into `out`; out_off
+ * (room for n+1) receives kept+1 offsets relative to `out`, starting at 0; index (room
+ * for n; may be NULL) the kept blobs' original indices.  It synchronises `stream` once
+ * to return *kept and *kept_bytes (host).  out == NULL: count only.  kept_bytes >
+ * out_cap: K2H_AMD_EINVAL with both counts set and nothing written.
+ *
+ * Both: n == 0 returns K2H_AMD_OK with no device work. */
+#define K2H_AMD_RALLE_OK 0
+#define K2H_AMD_RALLE_BAD_SPAN 1
+#define K2H_AMD_RALLE_EMPTY 2
+#define K2H_AMD_RALLE_NO_KEY 3
+#define K2H_AMD_RALLE_BAD_RANGE 4
+#define K2H_AMD_RALLE_BAD_HASH 5
+#define K2H_AMD_RALLE_BAD_SUBHASH 6
+#define K2H_AMD_ROUTE_TARGET 0x1u /* route bit 0 */
+#define K2H_AMD_ROUTE_OLD 0x2u    /* route bit 1 */
+
+typedef struct k2h_amd_hash_range {
+  uint64_t target_hash, target_max_hash;
+  int64_t target_hash_range;
+  uint64_t old_hash, old_max_hash; /* old_hash == ~0: no old range */
+} k2h_amd_hash_range;
+
+int k2h_amd_ralledata_check(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                            const k2h_amd_hash_range* range, uint32_t flags, uint8_t* status, uint8_t* route,
+                            uint64_t* h1, uint64_t* h2, void* stream);
+int k2h_amd_ralledata_select(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                             const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
+                             uint64_t* kept, uint64_t* kept_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * 5. Bulk key streams: keys anywhere in a buffer, and k2hash archives.
  *

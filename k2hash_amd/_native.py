@@ -34,6 +34,18 @@ class Table(ctypes.Structure):
 
 _tp = ctypes.POINTER(Table)
 
+
+class HashRange(ctypes.Structure):
+    """k2h_amd_hash_range (include/k2hash_amd.h section 4b): the arguments of
+    K2HShm::GetElementListToBinary's selection (lib/k2hshmdirect.cc:103, 118-131)."""
+    _fields_ = [("target_hash", ctypes.c_uint64), ("target_max_hash", ctypes.c_uint64),
+                ("target_hash_range", ctypes.c_int64), ("old_hash", ctypes.c_uint64),
+                ("old_max_hash", ctypes.c_uint64)]
+
+
+_rp = ctypes.POINTER(HashRange)
+_u64p = ctypes.POINTER(ctypes.c_uint64)
+
 # name -> (restype, argtypes); mirrors include/k2hash_amd.h
 SIGNATURES = {
     "k2h_hash": (_u64, [_p, ctypes.c_size_t]),
@@ -53,6 +65,8 @@ SIGNATURES = {
     "k2h_amd_build_ralledata": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _u64, _p, _p, ctypes.c_uint32, _p]),
     "k2h_amd_build_ralledata_host": (ctypes.c_int,
                                      [_p, _p, _p, _p, _p, _p, _p, _p, _u64, _p, _p, ctypes.c_uint32, ctypes.c_int]),
+    "k2h_amd_ralledata_check": (ctypes.c_int, [_p, _u64, _p, _u64, _rp, ctypes.c_uint32, _p, _p, _p, _p, _p]),
+    "k2h_amd_ralledata_select": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _p, _u64p, _u64p, _p]),
     "k2h_amd_hash_ranges": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_scan": (ctypes.c_int, [_p, _u64, _p, _u64, _p]),
     "k2h_amd_archive_prehash_host": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, ctypes.c_uint32, ctypes.c_int]),

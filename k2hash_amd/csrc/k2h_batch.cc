@@ -772,6 +772,60 @@ __attribute__((visibility("default"))) int k2h_amd_build_ralledata_host(
   return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "build_ralledata_host", e);
 }
 
+// ---------------------------------------------------------------------------
+// RALLEDATA consumer side (include/k2hash_amd.h section 4b).  Arguments are judged before
+// the device gate, so a bad call fails the same way with or without a GPU.
+// ---------------------------------------------------------------------------
+__attribute__((visibility("default"))) int k2h_amd_ralledata_check(const void* blobs, uint64_t size,
+                                                                   const uint64_t* blob_off, uint64_t n,
+                                                                   const k2h_amd_hash_range* range, uint32_t flags,
+                                                                   uint8_t* status, uint8_t* route, uint64_t* h1,
+                                                                   uint64_t* h2, void* stream) {
+  if (flags & K2H_AMD_FLAG_CSTR) return fail(K2H_AMD_EINVAL, "ralledata_check: blob keys are hashed as stored");
+  if (n == 0) return K2H_AMD_OK;
+  if (!blobs || !blob_off || !status) return fail(K2H_AMD_EINVAL, "ralledata_check: NULL blobs/blob_off/status");
+  if ((range != nullptr) != (route != nullptr))
+    return fail(K2H_AMD_EINVAL, "ralledata_check: range and route go together");
+  k2h::RalleRoute rr;
+  if (range) {
+    if (range->target_max_hash == 0) return fail(K2H_AMD_EINVAL, "ralledata_check: target_max_hash is 0");
+    // lib/k2hshmdirect.cc:118-119; the sums wrap in 64 bits
+    const uint64_t add = range->target_hash_range > 0 ? (uint64_t)range->target_hash_range - 1 : 0;
+    rr.t = range->target_hash;
+    rr.t_max = range->target_max_hash;
+    rr.t_end = (range->target_hash + add) % range->target_max_hash;
+    rr.old_on = range->old_hash != ~0ull;
+    if (rr.old_on) {
+      if (range->old_max_hash == 0) return fail(K2H_AMD_EINVAL, "ralledata_check: old_max_hash is 0");
+      rr.o = range->old_hash;
+      rr.o_max = range->old_max_hash;
+      rr.o_end = (range->old_hash + add) % range->old_max_hash;
+    }
+  }
+  K2H_GATE();
+  hipError_t e = k2h::launch_ralledata_check(blobs, size, blob_off, n, seed_for(flags), rr, status, route, h1, h2,
+                                             (hipStream_t)stream);
+  return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "launch_ralledata_check", e);
+}
+
+__attribute__((visibility("default"))) int k2h_amd_ralledata_select(const void* blobs, uint64_t size,
+                                                                    const uint64_t* blob_off, uint64_t n,
+                                                                    const uint8_t* keep, void* out, uint64_t out_cap,
+                                                                    uint64_t* out_off, uint64_t* index, uint64_t* kept,
+                                                                    uint64_t* kept_bytes, void* stream) {
+  if (!kept || !kept_bytes) return fail(K2H_AMD_EINVAL, "ralledata_select: NULL kept/kept_bytes");
+  *kept = *kept_bytes = 0;
+  if (n == 0) return K2H_AMD_OK;
+  if (!blobs || !blob_off || !keep || (out && !out_off))
+    return fail(K2H_AMD_EINVAL, "ralledata_select: NULL blobs/blob_off/keep/out_off");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_ralledata_select(blobs, size, blob_off, n, keep, out, out_cap, out_off, index, kept, kept_bytes,
+                                        (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EHIP || rc == K2H_AMD_ENOMEM) return fail(rc, "launch_ralledata_select", e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "ralledata_select: the kept blobs exceed out_cap, or too many blobs");
+}
+
 __attribute__((visibility("default"))) const char* k2h_amd_version(void) {
   return "k2hash_amd 0.1 (FNV-1A BUILTIN, gfx950 HIP batch kernels)";
 }

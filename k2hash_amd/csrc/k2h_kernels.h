@@ -109,6 +109,22 @@ struct RalleInputs {
 hipError_t launch_ralledata(const RalleInputs& in, uint64_t n, uint64_t seed, uint8_t* out, uint64_t* blob_off,
                             hipStream_t stream);
 
+// RALLEDATA consumer side (k2h_ralledata_check.hip).  RalleRoute is k2h_amd_hash_range with
+// the two range ends already reduced (lib/k2hshmdirect.cc:118-119): t / o the target / old
+// range's start, *_end its end, *_max its modulus; old_on = 0 when old_hash is ~0.
+struct RalleRoute {
+  uint64_t t = 0, t_end = 0, t_max = 1;
+  uint64_t o = 0, o_end = 0, o_max = 1;
+  uint32_t old_on = 0;
+};
+hipError_t launch_ralledata_check(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                                  uint64_t seed, const RalleRoute& route, uint8_t* status, uint8_t* route_out,
+                                  uint64_t* h1, uint64_t* h2, hipStream_t stream);
+// Returns a K2H_AMD_* code (the HIP error in *herr) and synchronises the stream once.
+int launch_ralledata_select(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                            const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
+                            uint64_t* kept, uint64_t* kept_bytes, hipStream_t stream, hipError_t* herr);
+
 // Keys at arbitrary (start, length) ranges (k2h_ranges.hip); cstr: hash key + NUL.
 hipError_t launch_ranges(const void* base, const uint64_t* starts, const uint64_t* lens, uint64_t n, uint64_t seed,
                          bool cstr, uint64_t* h1, uint64_t* h2, hipStream_t stream);

@@ -1,5 +1,6 @@
 """RALLEDATA producer: packed direct-set blobs with precomputed
-hashes, built on the GPU (include/k2hash_amd.h section 4).
+hashes, built on the GPU (include/k2hash_amd.h section 4), and the consumer side: a blob
+stream checked, routed by hash range and compacted on the GPU (section 4b).
 
 A blob is what K2HShm::GetElementToBinary writes (lib/k2hshmdirect.cc:59-88) on the
 packed struct of lib/k2hshmdirect.h:36-47, and what k2h_set_element_by_binary
@@ -118,3 +119,115 @@ def build_ralledata_host(keys: Sequence[bytes], vals=None, skeys=None, attrs=Non
                                                           FLAG_STD_FNV if std_fnv else 0, device)
     _native.check(rc)
     return out[:total], boff
+
+
+# ------------------------------------------------------------------ the consumer side
+# status[i] of check_ralledata (K2H_AMD_RALLE_*): the first that applies, in this order
+OK, BAD_SPAN, EMPTY, NO_KEY, BAD_RANGE, BAD_HASH, BAD_SUBHASH = range(7)
+STATUS_NAMES = ("OK", "BAD_SPAN", "EMPTY", "NO_KEY", "BAD_RANGE", "BAD_HASH", "BAD_SUBHASH")
+ROUTE_TARGET, ROUTE_OLD = 1, 2  # route[i] bits: the stored hash is in the target / the old range
+NO_OLD_HASH = (1 << 64) - 1     # old_hash of a HashRange without an old range (lib/k2hshmdirect.cc:119)
+
+HashRange = _native.HashRange
+
+
+def make_hash_range(target_hash: int, target_max_hash: int, target_hash_range: int = 1, old_hash: int = NO_OLD_HASH,
+                    old_max_hash: int = 0) -> HashRange:
+    """The selection arguments of K2HShm::GetElementListToBinary (lib/k2hshmdirect.cc:103)."""
+    return HashRange(target_hash, target_max_hash, target_hash_range, old_hash, old_max_hash)
+
+
+class CheckResult(NamedTuple):
+    status: object           # uint8 tensor, n
+    route: Optional[object]  # uint8 tensor, n (None without a hash range)
+    h1: Optional[object]     # int64 tensors, n: the recomputed hashes (None unless want_hashes)
+    h2: Optional[object]
+
+
+def _check_stream(blobs, blob_off, torch):
+    _check_dev(blobs, "blobs", torch.uint8)
+    _check_dev(blob_off, "blob_off", torch.int64)
+    if blob_off.device != blobs.device:
+        raise ValueError("blobs and blob_off are on different devices")
+    if blob_off.numel() < 1:
+        raise ValueError("blob_off needs n + 1 entries")
+    return blob_off.numel() - 1
+
+
+def check_ralledata(blobs, blob_off, hash_range: Optional[HashRange] = None, std_fnv: bool = False,
+                    want_hashes: bool = False, stream=None) -> CheckResult:
+    """Verify a blob stream on the device (k2h_amd_ralledata_check): blob i =
+    blobs[blob_off[i], blob_off[i+1]).  status[i] is OK or the first of BAD_SPAN ..
+    BAD_SUBHASH that applies; with `hash_range`, route[i] carries ROUTE_TARGET / ROUTE_OLD for
+    the blobs whose status is OK.  Asynchronous on the stream."""
+    torch = _torch()
+    n = _check_stream(blobs, blob_off, torch)
+    dev = blobs.device
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    route = torch.empty(n, dtype=torch.uint8, device=dev) if hash_range is not None else None
+    h1 = torch.empty(n, dtype=torch.int64, device=dev) if want_hashes else None
+    h2 = torch.empty(n, dtype=torch.int64, device=dev) if want_hashes else None
+    opt = lambda t: _dev_ptr(t) if t is not None else None  # noqa: E731
+    rc = _native.batch_lib().k2h_amd_ralledata_check(
+        ctypes.c_void_p(blobs.data_ptr() or 1), blobs.numel(), _dev_ptr(blob_off), n,
+        ctypes.byref(hash_range) if hash_range is not None else None, FLAG_STD_FNV if std_fnv else 0,
+        _dev_ptr(status), opt(route), opt(h1), opt(h2), _stream_handle(stream))
+    _native.check(rc)
+    return CheckResult(status, route, h1, h2)
+
+
+class Selected(NamedTuple):
+    blobs: object     # uint8 tensor: the kept blobs back to back (None when only counting)
+    blob_off: object  # int64 tensor, kept + 1, relative to `blobs`, from 0
+    index: object     # int64 tensor, kept: the kept blobs' indices in the input stream
+    kept: int
+    kept_bytes: int
+
+
+def select_ralledata(blobs, blob_off, keep, out=None, count_only: bool = False, want_index: bool = True,
+                     stream=None) -> Selected:
+    """Pack the blobs with keep[i] != 0 (and a valid span) back to back, in order
+    (k2h_amd_ralledata_select).  keep: uint8 or bool tensor of n.  Without `out` the kept
+    bytes are counted first and an exact buffer is allocated (two calls, each synchronising
+    the stream once); an `out` too small for them raises with nothing written.
+    count_only: only the counts (blobs, blob_off and index are None)."""
+    torch = _torch()
+    n = _check_stream(blobs, blob_off, torch)
+    if keep.dtype == torch.bool:
+        keep = keep.view(torch.uint8)
+    _check_dev(keep, "keep", torch.uint8)
+    if keep.numel() != n or keep.device != blobs.device:
+        raise ValueError("keep needs n entries on the blobs' device")
+    dev = blobs.device
+    lib = _native.batch_lib()
+    kept, kept_bytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(o, cap, ooff, idx):
+        return lib.k2h_amd_ralledata_select(
+            ctypes.c_void_p(blobs.data_ptr() or 1), blobs.numel(), _dev_ptr(blob_off), n, _dev_ptr(keep), o, cap,
+            ooff, idx, ctypes.byref(kept), ctypes.byref(kept_bytes), _stream_handle(stream))
+    if count_only or out is None:
+        _native.check(call(None, 0, None, None))
+        if count_only:
+            return Selected(None, None, None, int(kept.value), int(kept_bytes.value))
+        out = torch.empty(max(int(kept_bytes.value), 1), dtype=torch.uint8, device=dev)
+    else:
+        _check_dev(out, "out", torch.uint8)
+        if out.device != dev:
+            raise ValueError("out is on another device than the blobs")
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    index = torch.empty(n, dtype=torch.int64, device=dev) if want_index else None
+    _native.check(call(_dev_ptr(out), out.numel(), _dev_ptr(out_off), _dev_ptr(index) if want_index else None))
+    k, kb = int(kept.value), int(kept_bytes.value)
+    return Selected(out[:kb], out_off[:k + 1], index[:k] if want_index else None, k, kb)
+
+
+def route_ralledata(blobs, blob_off, hash_range: HashRange, std_fnv: bool = False, stream=None):
+    """What a receiver that owns `hash_range` does with a stream: check it, then keep the
+    blobs that are OK and whose hash is in the target range (status == 0 and route & 1).
+    Returns (Selected, CheckResult); the kept blobs feed k2h_set_element_by_binary."""
+    torch = _torch()
+    res = check_ralledata(blobs, blob_off, hash_range, std_fnv=std_fnv, stream=stream)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        keep = ((res.status == OK) & ((res.route & ROUTE_TARGET) != 0)).to(torch.uint8)
+    return select_ralledata(blobs, blob_off, keep, stream=stream), res
