@@ -260,6 +260,67 @@ int k2h_amd_ralledata_select(const void* blobs, uint64_t size, const uint64_t* b
                              const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
                              uint64_t* kept, uint64_t* kept_bytes, void* stream);
 
+/* 4c. Blobs straight from scanned records: the middle of a bulk load whose file is already
+ * in device memory.  The device scans of section 5 (k2h_amd_import_scan_device,
+ * k2h_amd_archive_scan_device and their _scan_prehash_device forms) report every record as
+ * offsets and lengths into the file; these two calls turn such records into the blobs of
+ * section 4 without a CSR copy of the payload in between.  (The record types are declared
+ * in section 5.)
+ *
+ * file, recs, out and blob_off are device pointers; blob_off has n+1 entries and is
+ * required; total is a host pointer and is required.  Blobs are packed back to back in
+ * record order: blob i = out[blob_off[i], blob_off[i+1]), blob_off[0] = 0, *total =
+ * blob_off[n].  A record that yields no blob contributes 0 bytes (blob_off[i+1] ==
+ * blob_off[i]); there is no separate index array.  That is exactly a stream
+ * k2h_amd_ralledata_check / _select accept (a 0-byte blob is BAD_SPAN there).
+ *
+ * k2h_amd_import_ralledata: every record yields a blob that holds the two C strings
+ * K2HShm::Set(const char*, const char*) stores and hashes (lib/k2hshm.cc:2081-2083):
+ *   key    = file[key_off, key_off+key_len) followed by one 0x00 byte, key_length = key_len+1
+ *   value  = file[val_off, val_off+val_len) followed by one 0x00 byte, val_length = val_len+1
+ *   skey_length = attrs_length = 0
+ *   key_pos = 80, val_pos = 80 + key_length, skey_pos = attrs_pos = val_pos + val_length
+ *   hash / subhash = k2h_hash / k2h_second_hash of key + NUL (the values of
+ *   k2h_amd_import_prehash); an empty key gives the 1-byte key "\0" with subhash == hash.
+ * The 0x00 bytes are written, never copied (the file byte after a key is a TAB or a
+ * newline).  A record is skipped (0 bytes) when its key range or its value range is not
+ * inside [0, size): off <= size && len <= size - off per range (recs are the caller's).
+ *
+ * k2h_amd_archive_ralledata: a record yields a blob only when status == 0, type == 0
+ * (SCOM_SET_ALL, the one record type that is a whole element, lib/k2harchive.cc:328-329),
+ * key_len > 0 (lib/k2hshmdirect.cc:355) and its key, value, subkeys and attrs ranges are
+ * each inside the file (the same test).  The four segments are copied as stored and hashed
+ * as stored; exdata is ignored.  Every other record gives 0 bytes.  A blob with a key and
+ * nothing else inserts nothing (lib/k2hshmdirect.cc:438); it is still emitted, with a
+ * faithful layout.
+ *
+ * K2H_AMD_FLAG_STD_FNV is honoured; K2H_AMD_FLAG_CSTR returns K2H_AMD_EINVAL (the import
+ * form is always key + NUL, the archive form always as stored).
+ *
+ * Flow: a sizing kernel and an exclusive sum fill blob_off, `stream` is synchronised once
+ * to return *total, then the blobs are built asynchronously on `stream`.  out == NULL:
+ * sizes only.  *total > out_cap: K2H_AMD_EINVAL with *total and blob_off set and nothing
+ * written to out.  n == 0: K2H_AMD_OK, *total = 0, blob_off[0] = 0 if blob_off is given,
+ * no other device work.  n so large that n * (82 + 4 * size) overflows 64 bits, a NULL
+ * total, or a NULL blob_off with n > 0: K2H_AMD_EINVAL, judged on the host.
+ *
+ * No byte outside [0, size) of the file is read except within the aligned 16 bytes that
+ * hold a valid byte, nothing of a skipped record's ranges is read, and nothing outside
+ * out[0, *total) and blob_off[0..n] is written.
+ *
+ * Parity: the layout is pinned by the fixture of oracle/gen_ralledata.cc and the hashes by
+ * the reference build of lib/k2hashfunc.cc.  That these blobs equal what
+ * K2HShm::GetElementToBinary would emit after Set / ReplaceAll of the same records is a
+ * restatement: libk2hash itself is not built by this project's tests. */
+struct k2h_amd_import_rec;  /* section 5 */
+struct k2h_amd_archive_rec; /* section 5 */
+int k2h_amd_import_ralledata(const void* file, uint64_t size, const struct k2h_amd_import_rec* recs, uint64_t n,
+                             void* out, uint64_t out_cap, uint64_t* blob_off, uint64_t* total, uint32_t flags,
+                             void* stream);
+int k2h_amd_archive_ralledata(const void* file, uint64_t size, const struct k2h_amd_archive_rec* recs, uint64_t n,
+                              void* out, uint64_t out_cap, uint64_t* blob_off, uint64_t* total, uint32_t flags,
+                              void* stream);
+
 /* ---------------------------------------------------------------------------
  * 5. Bulk key streams: keys anywhere in a buffer, and k2hash archives.
  *

@@ -826,6 +826,69 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_select(const void* 
   return rc == K2H_AMD_OK ? rc : fail(rc, "ralledata_select: the kept blobs exceed out_cap, or too many blobs");
 }
 
+// ---------------------------------------------------------------------------
+// RALLEDATA blobs from range records (include/k2hash_amd.h section 4c).  Arguments are judged
+// before the device gate, so a bad call fails the same way with or without a GPU.
+// ---------------------------------------------------------------------------
+namespace {
+
+// What both forms check on the host; returns > 0 when the call is already answered.
+int recs_ralledata_args(const char* who, const void* file, uint64_t size, const void* recs, uint64_t n,
+                        uint64_t* blob_off, uint64_t* total, uint32_t flags, void* stream, int* rc) {
+  static thread_local char msg[96];
+  auto bad = [&](const char* what) {
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    *rc = fail(K2H_AMD_EINVAL, msg);
+    return 1;
+  };
+  if (flags & K2H_AMD_FLAG_CSTR) return bad("the terminators are fixed by the form, not by K2H_AMD_FLAG_CSTR");
+  if (!total) return bad("NULL total");
+  *total = 0;
+  if (n == 0) {
+    *rc = K2H_AMD_OK;
+    if (blob_off) {
+      if ((*rc = gate_current())) return 1;
+      hipError_t e = hipMemsetAsync(blob_off, 0, 8, (hipStream_t)stream);
+      if (e != hipSuccess) *rc = fail(K2H_AMD_EHIP, who, e);
+    }
+    return 1;
+  }
+  if (!blob_off || !recs || (size && !file)) return bad("NULL file/recs/blob_off");
+  // a blob is at most 80 + 2 + 2 size (import) or 80 + 4 size (archive) bytes
+  if (size > (~0ull - 82) / 4 || n > ~0ull / (82 + 4 * size)) return bad("n blobs of this file overflow 64 bits");
+  return 0;
+}
+
+}  // namespace
+
+__attribute__((visibility("default"))) int k2h_amd_import_ralledata(const void* file, uint64_t size,
+                                                                    const k2h_amd_import_rec* recs, uint64_t n,
+                                                                    void* out, uint64_t out_cap, uint64_t* blob_off,
+                                                                    uint64_t* total, uint32_t flags, void* stream) {
+  int rc = K2H_AMD_OK;
+  if (recs_ralledata_args("import_ralledata", file, size, recs, n, blob_off, total, flags, stream, &rc)) return rc;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  rc = k2h::launch_import_ralledata(file, size, recs, n, seed_for(flags), out, out_cap, blob_off, total,
+                                    (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EHIP) return fail(rc, "launch_import_ralledata", e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "import_ralledata: the blobs exceed out_cap, or too many records");
+}
+
+__attribute__((visibility("default"))) int k2h_amd_archive_ralledata(const void* file, uint64_t size,
+                                                                     const k2h_amd_archive_rec* recs, uint64_t n,
+                                                                     void* out, uint64_t out_cap, uint64_t* blob_off,
+                                                                     uint64_t* total, uint32_t flags, void* stream) {
+  int rc = K2H_AMD_OK;
+  if (recs_ralledata_args("archive_ralledata", file, size, recs, n, blob_off, total, flags, stream, &rc)) return rc;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  rc = k2h::launch_archive_ralledata(file, size, recs, n, seed_for(flags), out, out_cap, blob_off, total,
+                                     (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EHIP) return fail(rc, "launch_archive_ralledata", e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "archive_ralledata: the blobs exceed out_cap, or too many records");
+}
+
 __attribute__((visibility("default"))) const char* k2h_amd_version(void) {
   return "k2hash_amd 0.1 (FNV-1A BUILTIN, gfx950 HIP batch kernels)";
 }

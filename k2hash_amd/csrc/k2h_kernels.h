@@ -125,6 +125,19 @@ int launch_ralledata_select(const void* blobs, uint64_t size, const uint64_t* bl
                             const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
                             uint64_t* kept, uint64_t* kept_bytes, hipStream_t stream, hipError_t* herr);
 
+// RALLEDATA blobs from range records (k2h_ralledata_recs.hip): the records of a scanned
+// import file (key + NUL, value + NUL) or archive (SCOM_SET_ALL records as stored) become
+// blobs packed in record order, a record that yields none taking 0 bytes; blob_off (n + 1,
+// required) by a sizing kernel and an exclusive sum.  Both return a K2H_AMD_* code (the HIP
+// error in *herr) and synchronise the stream once to return *total; out == NULL: sizes only;
+// *total > out_cap: K2H_AMD_EINVAL with nothing written to out.  n >= 1.
+int launch_import_ralledata(const void* file, uint64_t size, const k2h_amd_import_rec* recs, uint64_t n, uint64_t seed,
+                            void* out, uint64_t out_cap, uint64_t* blob_off, uint64_t* total, hipStream_t stream,
+                            hipError_t* herr);
+int launch_archive_ralledata(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
+                             uint64_t seed, void* out, uint64_t out_cap, uint64_t* blob_off, uint64_t* total,
+                             hipStream_t stream, hipError_t* herr);
+
 // Keys at arbitrary (start, length) ranges (k2h_ranges.hip); cstr: hash key + NUL.
 hipError_t launch_ranges(const void* base, const uint64_t* starts, const uint64_t* lens, uint64_t n, uint64_t seed,
                          bool cstr, uint64_t* h1, uint64_t* h2, hipStream_t stream);

@@ -25,39 +25,17 @@
 
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
+#include "k2h_ralle_pieces.h"
 
 namespace k2h {
 namespace {
-
-// Workgroup barrier over LDS only (see its use in ralledata_gather_kernel).
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ uint64_t seg_len(const uint64_t* off, uint64_t i) { return off ? off[i + 1] - off[i] : 0; }
 __device__ __forceinline__ uint64_t seg_before(const uint64_t* off, uint64_t i) { return off ? off[i] - off[0] : 0; }
 
 
-// Group form (oversize tiles): G lanes per record, 64/G records per wave.  Lane q of a group
-// writes header piece q (5 x 16 B) and copies bytes [16q + 16Gj, +16) of each segment,
-// so a group's loads and stores are consecutive 16-byte pieces instead of one lane
-// streaming a whole record.  A segment's last partial piece is the 16 bytes ENDING at
-// its last byte (they overlap the previous piece with the same bytes, so the order of
-// the two stores does not matter); only segments shorter than 16 bytes are copied byte
-// by byte.  G = 8 keeps most lanes busy on BASELINE-like records (keys 8-64 B, values
-// 0-256 B).
-template <int G>
-__device__ __forceinline__ void group_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint64_t len,
-                                           uint32_t q) {
-  uint64_t full = len & ~15ull;
-  for (uint64_t j = 16ull * q; j < full; j += 16ull * G)
-    *reinterpret_cast<u32x4_ua*>(dst + j) = *reinterpret_cast<const u32x4_ua*>(src + j);
-  if (full == len) return;
-  if (len >= 16) {
-    if (q == G - 1)
-      *reinterpret_cast<u32x4_ua*>(dst + len - 16) = *reinterpret_cast<const u32x4_ua*>(src + len - 16);
-    return;
-  }
-  for (uint64_t t = full + q; t < len; t += G) dst[t] = src[t];  // the <= 15 tail bytes
-}
+// (lds_sync, group_copy and seg_pack / seg_unpack: k2h_ralle_pieces.h, shared with the
+// range-record producer)
 
 // Gather form (round 2): output-driven.  A block takes R consecutive records; its blobs are
 // one contiguous output span, and the records' key / value / subkey / attribute bytes are
@@ -152,10 +130,6 @@ __device__ __forceinline__ void staged_key_hash(const uint8_t* end, uint32_t len
 // meets at most 14 records -- every record carries an 80-byte header -- so fewer than 256
 // segments, and the low byte and the run's base recover the index) -- where the round-2
 // tables (int2, uint16) allowed 7 (A/B: 0.724 vs 0.733 ms, profiles/r03ad_ralle_ab.txt).
-__device__ __forceinline__ uint32_t seg_pack(int32_t adj, int32_t end) {
-  return (uint32_t)(uint16_t)(int16_t)adj | ((uint32_t)end << 16);
-}
-__device__ __forceinline__ int2 seg_unpack(uint32_t v) { return int2{(int32_t)(int16_t)(v & 0xffffu), (int32_t)(v >> 16)}; }
 
 // KV: no subkeys and no attributes (both offset arrays NULL, the common direct-set call):
 // the two empty streams fold away at compile time -- half the block-uniform setup (64-bit

@@ -1,6 +1,8 @@
 """RALLEDATA producer: packed direct-set blobs with precomputed
 hashes, built on the GPU (include/k2hash_amd.h section 4), and the consumer side: a blob
-stream checked, routed by hash range and compacted on the GPU (section 4b).
+stream checked, routed by hash range and compacted on the GPU (section 4b); and the hop
+between the device scans and those two: blobs built straight from the range records of a
+scanned import file or archive (section 4c).
 
 A blob is what K2HShm::GetElementToBinary writes (lib/k2hshmdirect.cc:59-88) on the
 packed struct of lib/k2hshmdirect.h:36-47, and what k2h_set_element_by_binary
@@ -16,6 +18,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 
 from . import _native
+from .archive import import_scan_device
 from .batch import FLAG_STD_FNV, _check_dev, _dev_ptr, _stream_handle, _torch
 
 HEADER = 80  # sizeof(RALLEDATA)
@@ -119,6 +122,58 @@ def build_ralledata_host(keys: Sequence[bytes], vals=None, skeys=None, attrs=Non
                                                           FLAG_STD_FNV if std_fnv else 0, device)
     _native.check(rc)
     return out[:total], boff
+
+
+# ------------------------------------------------------------ blobs from scanned records
+def _recs_to_ralledata(name: str, width: int, file, recs, std_fnv: bool, stream):
+    torch = _torch()
+    _check_dev(file, "file", torch.uint8)
+    _check_dev(recs, "recs", torch.int64)
+    if recs.dim() != 2 or recs.shape[1] != width:
+        raise ValueError(f"recs must be a contiguous (n, {width}) int64 tensor")
+    if recs.device != file.device:
+        raise ValueError("file and recs are on different devices")
+    n = recs.shape[0]
+    fn = getattr(_native.batch_lib(), name)
+    fp, rp = ctypes.c_void_p(file.data_ptr() or 1), ctypes.c_void_p(recs.data_ptr() or 1)
+    blob_off = torch.empty(n + 1, dtype=torch.int64, device=file.device)
+    total = ctypes.c_uint64(0)
+    flags = FLAG_STD_FNV if std_fnv else 0
+
+    def call(out, cap):
+        _native.check(fn(fp, file.numel(), rp, n, out, cap, _dev_ptr(blob_off), ctypes.byref(total), flags,
+                         _stream_handle(stream)))
+    call(None, 0)  # sizes only
+    out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=file.device)
+    if total.value:
+        call(_dev_ptr(out), out.numel())
+    return out[:int(total.value)], blob_off
+
+
+def import_to_ralledata(file, recs, std_fnv: bool = False, stream=None):
+    """Blobs of the records of a k2himport file in device memory (k2h_amd_import_ralledata):
+    `recs` is the (n, 4) int64 tensor of import_scan_device.  Every record becomes the blob of
+    key + NUL and value + NUL, the strings K2HShm::Set(const char*, const char*) stores, with
+    the hashes of key + NUL; a record whose ranges leave the file becomes a 0-byte blob.
+    Returns (blobs, blob_off): uint8 and int64 (n + 1) device tensors, blob i =
+    blobs[blob_off[i]:blob_off[i + 1]], in record order.  Two calls (size, then build), each
+    synchronising the stream once."""
+    return _recs_to_ralledata("k2h_amd_import_ralledata", 4, file, recs, std_fnv, stream)
+
+
+def archive_to_ralledata(file, recs, std_fnv: bool = False, stream=None):
+    """Blobs of the SCOM_SET_ALL records of a k2hash archive in device memory
+    (k2h_amd_archive_ralledata): `recs` is the (n, 13) int64 tensor of archive.scan_device.
+    A record with status 0, type 0, a key and all four ranges inside the file becomes the
+    blob of its segments as stored; every other record becomes a 0-byte blob.  Returns
+    (blobs, blob_off) as import_to_ralledata."""
+    return _recs_to_ralledata("k2h_amd_archive_ralledata", 13, file, recs, std_fnv, stream)
+
+
+def import_file_to_ralledata(file, fmt: str = "tsv", std_fnv: bool = False, stream=None):
+    """import_scan_device, then import_to_ralledata: a TSV or mdbm_export file in device
+    memory to its blob stream.  Returns (blobs, blob_off)."""
+    return import_to_ralledata(file, import_scan_device(file, fmt, stream=stream), std_fnv=std_fnv, stream=stream)
 
 
 # ------------------------------------------------------------------ the consumer side
