@@ -260,6 +260,54 @@ int k2h_amd_ralledata_select(const void* blobs, uint64_t size, const uint64_t* b
                              const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
                              uint64_t* kept, uint64_t* kept_bytes, void* stream);
 
+/* 4b'. Superseded duplicates: the blobs of a stream that k2h_set_element_by_binary need not
+ * be fed, because a later blob of the same stream undoes them.  Device pointers only (the
+ * stream arguments mean what they mean for k2h_amd_ralledata_check).
+ *
+ * Identity.  K2HShm::SetElementByBinArray finds the element a blob addresses from the
+ * blob's STORED hash (GetCKIndex, lib/k2hshmdirect.cc:373), its stored hash and subhash
+ * (GetElementList, :377) and its key bytes (GetElement, :378).  Two blobs address the same
+ * element exactly when stored hash, stored subhash, key_length and the key bytes are equal.
+ * The hash fields are trusted, not recomputed, as SetElementByBinArray trusts them.
+ *
+ * Rule.  Blob i is superseded when some later blob has i's identity -- call the nearest j --
+ * and both i and j have attrs_length == 0.  Feeding the stream without i then leaves the
+ * table that feeding it with i leaves, whatever the table held before: an absent element,
+ * one without an attrs page (K2HShm::GetAttrs gives NULL, lib/k2hshm.cc:2059-2073) or an
+ * expired one is overwritten by i, and i, having no attrs, is overwritten by j
+ * unconditionally; before a live element with an mtime both i and j return early
+ * (lib/k2hshmdirect.cc:402-405 when it is newer than pts, :421-427 because neither has an
+ * mtime of its own).  A key-only blob (removes, inserts nothing, :438) takes the same
+ * paths.  A blob with attrs is never dropped and never causes a drop: whether it wins
+ * depends on the mtime and expiry inside its serialized K2HAttrs.
+ *
+ * Participants.  Blob i takes part when consider is NULL or consider[i] != 0, its span is
+ * good (not BAD_SPAN) and its header passes the header tests of k2h_amd_ralledata_check
+ * (not EMPTY, NO_KEY or BAD_RANGE).  All blobs of one identity get the same status and
+ * route from _check, so the two compose as consider[i] = (status[i] == OK && route bit).
+ *
+ *   keep[i]  (n entries, required) 0 for a non-participant and for a superseded
+ *            participant, 1 for every other participant
+ *   by[i]    (n entries, may be NULL) the nearest later participant of i's identity, whether
+ *            or not it supersedes i; ~0 when there is none, and for a non-participant
+ *   *dropped (host, may be NULL) the number of superseded blobs
+ *
+ * dropped == NULL: asynchronous on `stream`; else `stream` is synchronised once.  n == 0:
+ * K2H_AMD_OK, *dropped = 0, no device work.  K2H_AMD_EINVAL, judged on the host before any
+ * device is touched, each with its own message: keep, blobs or blob_off NULL with n > 0;
+ * n > 2^32 - 2 (indices are sorted as 32-bit values).
+ *
+ * No byte outside [0, size) is read except within the aligned 16 bytes that hold a valid
+ * byte; nothing of a non-participant beyond its header, and no header of a blob whose
+ * span is bad.  Temporary device memory: about 56 bytes per blob plus the sort's own, kept
+ * per device between calls.  Cost: a gather pass over the headers, one library radix sort of
+ * (stored hash, index) pairs on the hash's low bits, and a resolve pass that reads only the
+ * keys of blobs whose stored hash occurs more than once; r DISTINCT keys under one stored
+ * hash cost O(r^2) key compares (a crafted stream, or one whose hash fields _check would
+ * have refused), and r stored hashes that agree in all their low bits O(r^2) walk steps. */
+int k2h_amd_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                            const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, void* stream);
+
 /* 4c. Blobs straight from scanned records: the middle of a bulk load whose file is already
  * in device memory.  The device scans of section 5 (k2h_amd_import_scan_device,
  * k2h_amd_archive_scan_device and their _scan_prehash_device forms) report every record as

@@ -67,6 +67,7 @@ SIGNATURES = {
                                      [_p, _p, _p, _p, _p, _p, _p, _p, _u64, _p, _p, ctypes.c_uint32, ctypes.c_int]),
     "k2h_amd_ralledata_check": (ctypes.c_int, [_p, _u64, _p, _u64, _rp, ctypes.c_uint32, _p, _p, _p, _p, _p]),
     "k2h_amd_ralledata_select": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _p, _u64p, _u64p, _p]),
+    "k2h_amd_ralledata_dedup": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _p]),
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_hash_ranges": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, ctypes.c_uint32, _p]),

@@ -826,6 +826,24 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_select(const void* 
   return rc == K2H_AMD_OK ? rc : fail(rc, "ralledata_select: the kept blobs exceed out_cap, or too many blobs");
 }
 
+// Section 4b': the superseded duplicates of a stream.  Judged on the host like the two above.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_dedup(const void* blobs, uint64_t size,
+                                                                   const uint64_t* blob_off, uint64_t n,
+                                                                   const uint8_t* consider, uint8_t* keep,
+                                                                   uint64_t* by, uint64_t* dropped, void* stream) {
+  if (dropped) *dropped = 0;
+  if (n == 0) return K2H_AMD_OK;
+  if (!keep) return fail(K2H_AMD_EINVAL, "ralledata_dedup: NULL keep");
+  if (!blobs) return fail(K2H_AMD_EINVAL, "ralledata_dedup: NULL blobs");
+  if (!blob_off) return fail(K2H_AMD_EINVAL, "ralledata_dedup: NULL blob_off");
+  if (n > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL, "ralledata_dedup: more than 2^32 - 2 blobs (indices are sorted as 32-bit values)");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_ralledata_dedup(blobs, size, blob_off, n, consider, keep, by, dropped, (hipStream_t)stream, &e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_dedup", e);
+}
+
 // ---------------------------------------------------------------------------
 // RALLEDATA blobs from range records (include/k2hash_amd.h section 4c).  Arguments are judged
 // before the device gate, so a bad call fails the same way with or without a GPU.

@@ -125,6 +125,12 @@ int launch_ralledata_select(const void* blobs, uint64_t size, const uint64_t* bl
                             const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
                             uint64_t* kept, uint64_t* kept_bytes, hipStream_t stream, hipError_t* herr);
 
+// Superseded duplicates of a blob stream (k2h_ralledata_dedup.hip).  Returns a K2H_AMD_* code
+// (the HIP error in *herr); synchronises the stream once when dropped != NULL.  1 <= n <= 2^32 - 2.
+int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                           const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, hipStream_t stream,
+                           hipError_t* herr);
+
 // RALLEDATA blobs from range records (k2h_ralledata_recs.hip): the records of a scanned
 // import file (key + NUL, value + NUL) or archive (SCOM_SET_ALL records as stored) become
 // blobs packed in record order, a record that yields none taking 0 bytes; blob_off (n + 1,

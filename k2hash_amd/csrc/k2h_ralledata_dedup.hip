@@ -1,0 +1,298 @@
+// k2hash_amd -- RALLEDATA consumer side: drop the superseded duplicates of a blob stream in
+// device memory (include/k2hash_amd.h section 4b').
+//
+// K2HShm::SetElementByBinArray (lib/k2hshmdirect.cc:343-478) finds the element a blob
+// addresses by the blob's STORED hash (GetCKIndex, :373), its stored hash and subhash
+// (GetElementList, :377) and its key bytes (GetElement, :378): those four -- hash, subhash,
+// key_length, key -- are the blob's identity.  Blob i is superseded when the nearest later
+// blob j of the same identity exists and neither i nor j carries attrs: whatever the table
+// held for that key, i either is overwritten by j unconditionally (an element without an attrs
+// page: GetAttrs gives NULL, lib/k2hshm.cc:2059-2073, so :382 is skipped) or returns early
+// exactly as j does (:402-405, :421-427).  A blob with attrs is never dropped and never
+// causes a drop.
+//
+// Three stages, all on the caller's stream:
+//   gather   one lane per blob: span, header and classify (k2h_ralle_header.h, shared with
+//            the check kernel); a participant leaves its stored hash and a 32-byte side
+//            record (subhash, absolute key offset, key length, attrs bit).  A scan of the
+//            tiles' participant counts and a second kernel lay the (hash, index) pairs out
+//            for the sort: participants first, in stream order, every other blob behind
+//            them as (~0, kNone) -- so a non-participant sorts behind every participant of
+//            any hash and ends every walk that reaches it.
+//   sort     hipcub::DeviceRadixSort::SortPairs over (hash, index), on the hash's low bits
+//            only (sort_bits_for): stable, so blobs of one stored hash are neighbours in
+//            stream order, now and then with a blob of another hash among them.
+//   resolve  one lane per sorted position p.  Other sorted bits at p + 1: the blob is kept
+//            and nothing more is read.  Else the lane walks forward from p + 1 to the first
+//            entry with its hash, subhash, key length and key bytes -- `by` -- and applies
+//            the attrs rule.
+//            A run of r equal keys costs O(1) per lane (the match is at p + 1).  A run of r
+//            DISTINCT keys under one stored hash costs O(r) per lane, O(r^2) in all: only a
+//            crafted stream (or one with wrong hash fields, which k2h_amd_ralledata_check
+//            finds) has such runs.
+//
+// Blob i = blobs[off[i], off[i+1]).  No byte outside [0, size) is read: a key is compared in
+// 16-byte chunks that END at its last byte, and it starts at or after byte 80 of its blob,
+// so chunk 0 never begins below the buffer and no chunk passes the key's end.  Nothing of a
+// non-participant is read beyond its header, and nothing of a blob whose span is bad or
+// whose `consider` byte is 0.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <stdint.h>
+
+#include <mutex>
+
+#include "k2h_endwalk.h"
+#include "k2h_kernels.h"
+#include "k2h_ralle_header.h"
+
+namespace k2h {
+namespace {
+
+constexpr int kDedupBlobs = 256;         // gather / compact: blobs per 256-thread block, one per thread
+constexpr int kResolveBlock = 256;       // resolve: sorted positions per block, one per thread
+constexpr uint32_t kNone = 0xFFFFFFFFu;  // the index of a pair that stands for a non-participant
+constexpr int kCounters = 64;            // resolve counts into this many words, each on a 64-byte line of its own
+
+// What resolve needs of a participant; 32 bytes, so one aligned sector per record.
+struct __attribute__((aligned(16))) Side {
+  uint64_t sub;    // stored subhash
+  uint64_t koff;   // the key's first byte, from `blobs`
+  uint64_t klen;   // >= 1
+  uint64_t attrs;  // 1: attrs_length != 0
+};
+static_assert(sizeof(Side) == 32, "two 16-byte loads");
+
+// keep[i] = 1 for a participant (resolve clears the superseded ones), by[i] = ~0; the
+// participant's stored hash to hash[i] and its side record to side[i]; the tile's count.
+__global__ __launch_bounds__(256) void ralledata_dedup_gather_kernel(
+    const uint8_t* __restrict__ blobs, uint64_t size, const uint64_t* __restrict__ off, uint64_t n,
+    const uint8_t* __restrict__ consider, uint8_t* __restrict__ keep, uint64_t* __restrict__ by,
+    uint64_t* __restrict__ hash, Side* __restrict__ side, uint64_t* __restrict__ tile_count) {
+  typedef hipcub::BlockReduce<uint32_t, kDedupBlobs> Reduce;
+  __shared__ typename Reduce::TempStorage tmp;
+  const uint64_t i = (uint64_t)blockIdx.x * kDedupBlobs + threadIdx.x;
+  uint32_t part = 0;
+  if (i < n && (!consider || consider[i])) {
+    const uint64_t b = off[i], e = off[i + 1];
+    if (e >= b && e <= size && e - b >= (uint64_t)kHdr) {
+      uint64_t f[10];
+      load_fields(blobs + b, f);
+      if (classify(f, e - b) == K2H_AMD_RALLE_OK) {
+        part = 1;
+        hash[i] = f[0];
+        side[i] = Side{f[1], b + f[6], f[2], f[5] ? 1ull : 0ull};
+      }
+    }
+  }
+  if (i < n) {
+    keep[i] = (uint8_t)part;
+    if (by) by[i] = ~0ull;
+  }
+  const uint32_t count = Reduce(tmp).Sum(part);
+  if (threadIdx.x == 0) tile_count[blockIdx.x] = count;
+}
+
+// The sort's input, n pairs: participant i at its rank among the participants, every other
+// blob behind all m of them (tile_base = the scanned tile counts, entry ntiles = m).
+__global__ __launch_bounds__(256) void ralledata_dedup_compact_kernel(
+    const uint8_t* __restrict__ keep, const uint64_t* __restrict__ hash, uint64_t n,
+    const uint64_t* __restrict__ tile_base, uint64_t ntiles, uint64_t* __restrict__ keys,
+    uint32_t* __restrict__ idx) {
+  typedef hipcub::BlockScan<uint32_t, kDedupBlobs> Scan;
+  __shared__ typename Scan::TempStorage tmp;
+  const uint64_t i = (uint64_t)blockIdx.x * kDedupBlobs + threadIdx.x;
+  const uint32_t part = i < n && keep[i] ? 1u : 0u;
+  uint32_t rank;
+  Scan(tmp).ExclusiveSum(part, rank);
+  if (i >= n) return;
+  const uint64_t before = tile_base[blockIdx.x] + rank;  // participants before blob i
+  const uint64_t pos = part ? before : tile_base[ntiles] + (i - before);
+  keys[pos] = part ? hash[i] : ~0ull;
+  idx[pos] = part ? (uint32_t)i : kNone;
+}
+
+__device__ __forceinline__ bool differ(uint4 x, uint4 y) {
+  return ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) != 0;
+}
+
+// Two keys of the same length kl >= 1, as ceil(kl / 16) chunks that end at each key's last
+// byte; the lead bytes of chunk 0 (bytes before the keys) are masked off.
+__device__ __forceinline__ bool same_key(const uint8_t* a, const uint8_t* b, uint64_t kl) {
+  const uint64_t k = (kl + 15) >> 4;
+  const uint32_t lead = (uint32_t)(16 * k - kl);
+  const uint8_t* ca = a + kl - 16 * k;
+  const uint8_t* cb = b + kl - 16 * k;
+  if (differ(mask_lead(ld16(ca), lead), mask_lead(ld16(cb), lead))) return false;
+  for (uint64_t q = 1; q < k; ++q)
+    if (differ(ld16(ca + 16 * q), ld16(cb + 16 * q))) return false;
+  return true;
+}
+
+// keys / idx: the pairs, sorted by the hash bits under `mask` (sort_bits_for).  Writes
+// keep[i] = 0 for a superseded blob and by[i] for every blob that has a later one of its
+// identity; counts the superseded into the kCounters words of `dropped` (their sum is the
+// count).
+__global__ __launch_bounds__(kResolveBlock) void ralledata_dedup_resolve_kernel(
+    const uint8_t* __restrict__ blobs, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+    uint64_t n, uint64_t mask, const Side* __restrict__ side, uint8_t* __restrict__ keep,
+    uint64_t* __restrict__ by, unsigned long long* __restrict__ dropped) {
+  const uint64_t p = (uint64_t)blockIdx.x * kResolveBlock + threadIdx.x;
+  bool drop = false;
+  if (p + 1 < n) {  // the last position has nothing behind it
+    const uint32_t i = idx[p];
+    const uint64_t h = keys[p];
+    if (i != kNone && !((keys[p + 1] ^ h) & mask) && idx[p + 1] != kNone) {
+      const Side a = side[i];
+      for (uint64_t q = p + 1; q < n; ++q) {
+        const uint64_t hq = keys[q];
+        if ((hq ^ h) & mask) break;
+        const uint32_t j = idx[q];
+        if (j == kNone) break;  // (sorted bits all ones: the non-participants follow the participants)
+        if (hq != h) continue;  // another hash with the same sorted bits
+        const Side b = side[j];
+        if (b.sub != a.sub || b.klen != a.klen || !same_key(blobs + a.koff, blobs + b.koff, a.klen)) continue;
+        if (by) by[i] = j;
+        drop = !(a.attrs | b.attrs);
+        break;
+      }
+      if (drop) keep[i] = 0;
+    }
+  }
+  // one atomic per wave, neighbouring waves on different lines: with every wave adding to one
+  // word the adds queue up behind each other and set the kernel's time
+  const unsigned long long m = __ballot(drop);
+  if ((threadIdx.x & 63u) == 0 && m) {
+    const uint32_t wave = blockIdx.x * (kResolveBlock / 64) + (threadIdx.x >> 6);
+    atomicAdd(dropped + 8 * (wave % kCounters), (unsigned long long)__popcll(m));
+  }
+}
+
+// The call's temporaries: one grow-only buffer per device, held across calls under a
+// per-device lock (the pattern of SelScratch, k2h_ralledata_check.hip) -- 56 bytes per blob
+// (two key and two index columns, the side records), the tile counts and their scan, the
+// counters, and the library's own storage.  The kernels still use the buffer after an
+// asynchronous call has returned, so each call leaves an event behind and the next call's
+// stream waits for it before it writes.
+struct DedupScratch {
+  std::mutex mu;
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t done = nullptr;
+};
+DedupScratch g_dedup[64];
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The low hash bits the pairs are sorted by: 8 more than the blobs' number has, in whole
+// bytes (the library sorts a byte per pass), at least 16.  Equal hashes are neighbours under
+// any number of bits, and the sort stays stable; with 8 spare bits about one pair of neighbours
+// in 256 shares the sorted bits without sharing the hash, and the walk steps over those.  At
+// 8 Mi blobs this is 32 bits, half the passes of a 64-bit sort.
+int sort_bits_for(uint64_t n) {
+  int bits = 0;
+  while (bits < 64 && (n - 1) >> bits) ++bits;
+  bits = (bits + 8 + 7) / 8 * 8;
+  return bits < 16 ? 16 : bits > 64 ? 64 : bits;
+}
+constexpr size_t kCounterBytes = 64 * kCounters;
+
+}  // namespace
+
+// Returns a K2H_AMD_* code (the HIP error, if any, in *herr); synchronises the stream once
+// when dropped != NULL, else not at all.  1 <= n <= 2^32 - 2.
+int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                           const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, hipStream_t stream,
+                           hipError_t* herr) {
+  *herr = hipSuccess;
+  const uint64_t nt = (n + kDedupBlobs - 1) / kDedupBlobs;
+  hipError_t e = hipSuccess;
+  auto tr = [&](hipError_t x) {
+    if (e == hipSuccess) e = x;
+  };
+  int dev = 0;
+  tr(hipGetDevice(&dev));
+  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  size_t scan_bytes = 0, sort_bytes = 0;
+  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
+  const int sort_bits = sort_bits_for(n);
+  tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
+  if (e != hipSuccess) {
+    *herr = e;
+    return K2H_AMD_EHIP;
+  }
+  const size_t c8 = align256(n * 8), c4 = align256(n * 4), cs = align256(n * sizeof(Side)), ct = align256((nt + 1) * 8);
+  const size_t tmp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
+  const size_t total = 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes + align256(tmp_bytes);
+  DedupScratch& sc = g_dedup[dev];
+  std::lock_guard<std::mutex> lk(sc.mu);
+  if (!sc.done) tr(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
+  if (e == hipSuccess && sc.bytes < total) {
+    if (sc.p) tr(hipFree(sc.p));  // waits for the device: no earlier call's kernel still uses it
+    sc.p = nullptr;
+    sc.bytes = 0;
+    const hipError_t a = e == hipSuccess ? hipMalloc(&sc.p, total) : e;
+    if (a == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      sc.p = nullptr;
+      *herr = a;
+      return K2H_AMD_ENOMEM;
+    }
+    tr(a);
+    if (e == hipSuccess) sc.bytes = total;
+  }
+  if (e == hipSuccess) tr(hipStreamWaitEvent(stream, sc.done, 0));  // never recorded: no wait
+  if (e != hipSuccess) {
+    *herr = e;
+    return K2H_AMD_EHIP;
+  }
+  uint8_t* base = (uint8_t*)sc.p;
+  uint64_t* keys_in = (uint64_t*)base;
+  uint64_t* keys_out = (uint64_t*)(base + c8);  // first the blobs' hashes by blob index, then the sorted keys
+  uint32_t* idx_in = (uint32_t*)(base + 2 * c8);
+  uint32_t* idx_out = (uint32_t*)(base + 2 * c8 + c4);
+  Side* side = (Side*)(base + 2 * c8 + 2 * c4);
+  uint64_t* tile_count = (uint64_t*)(base + 2 * c8 + 2 * c4 + cs);
+  uint64_t* tile_base = (uint64_t*)(base + 2 * c8 + 2 * c4 + cs + ct);
+  unsigned long long* counter = (unsigned long long*)(base + 2 * c8 + 2 * c4 + cs + 2 * ct);
+  void* tmp = base + 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes;
+  // entry nt of the counts is 0, so entry nt of their exclusive scan is the participants' number
+  tr(hipMemsetAsync(tile_count + nt, 0, 8, stream));
+  tr(hipMemsetAsync(counter, 0, kCounterBytes, stream));
+  if (e == hipSuccess) {
+    ralledata_dedup_gather_kernel<<<(unsigned)nt, kDedupBlobs, 0, stream>>>((const uint8_t*)blobs, size, blob_off, n,
+                                                                          consider, keep, by, keys_out, side,
+                                                                          tile_count);
+    tr(hipGetLastError());
+  }
+  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, tile_count, tile_base, nt + 1, stream));
+  if (e == hipSuccess) {
+    ralledata_dedup_compact_kernel<<<(unsigned)nt, kDedupBlobs, 0, stream>>>(keep, keys_out, n, tile_base, nt, keys_in,
+                                                                           idx_in);
+    tr(hipGetLastError());
+  }
+  if (e == hipSuccess)
+    tr(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint64_t*)keys_in, keys_out,
+                                          (const uint32_t*)idx_in, idx_out, n, 0, sort_bits, stream));
+  if (e == hipSuccess) {
+    const uint64_t grid = (n + kResolveBlock - 1) / kResolveBlock;
+    const uint64_t mask = sort_bits == 64 ? ~0ull : (1ull << sort_bits) - 1;
+    ralledata_dedup_resolve_kernel<<<(unsigned)grid, kResolveBlock, 0, stream>>>(
+        (const uint8_t*)blobs, keys_out, idx_out, n, mask, side, keep, by, counter);
+    tr(hipGetLastError());
+  }
+  unsigned long long counts[8 * kCounters];
+  if (e == hipSuccess && dropped) tr(hipMemcpyAsync(counts, counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
+  if (e == hipSuccess && dropped) {
+    tr(hipStreamSynchronize(stream));
+    uint64_t sum = 0;
+    for (int c = 0; c < kCounters; ++c) sum += counts[8 * c];
+    if (e == hipSuccess) *dropped = sum;
+  }
+  *herr = e;
+  return e != hipSuccess ? K2H_AMD_EHIP : K2H_AMD_OK;
+}
+
+}  // namespace k2h

@@ -277,12 +277,52 @@ def select_ralledata(blobs, blob_off, keep, out=None, count_only: bool = False, 
     return Selected(out[:kb], out_off[:k + 1], index[:k] if want_index else None, k, kb)
 
 
-def route_ralledata(blobs, blob_off, hash_range: HashRange, std_fnv: bool = False, stream=None):
+NO_LATER = (1 << 64) - 1  # by[i] of dedup_ralledata when no later blob has blob i's identity (-1 as int64)
+
+
+def dedup_ralledata(blobs, blob_off, consider=None, want_by: bool = False, count: bool = True, stream=None):
+    """The blobs of a stream worth feeding to k2h_set_element_by_binary
+    (k2h_amd_ralledata_dedup).  Two blobs have the same identity when their stored hash,
+    stored subhash, key length and key bytes are equal; blob i is superseded -- keep[i] = 0 --
+    when the nearest later blob of its identity exists and neither of the two carries attrs.
+    consider: uint8 or bool tensor of n, the blobs that take part (None: all); a blob that
+    does not, or whose span or header is bad, gets keep[i] = 0 and supersedes nothing.
+    Returns (keep, by, dropped): keep a uint8 tensor of n; by (want_by) an int64 tensor of n,
+    the nearest later participant of the same identity or -1 (NO_LATER as unsigned); dropped
+    (count) the number of superseded blobs, which synchronises the stream once -- with
+    count=False the call is asynchronous and dropped is None."""
+    torch = _torch()
+    n = _check_stream(blobs, blob_off, torch)
+    dev = blobs.device
+    if consider is not None:
+        if consider.dtype == torch.bool:
+            consider = consider.view(torch.uint8)
+        _check_dev(consider, "consider", torch.uint8)
+        if consider.numel() != n or consider.device != dev:
+            raise ValueError("consider needs n entries on the blobs' device")
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    by = torch.empty(n, dtype=torch.int64, device=dev) if want_by else None
+    dropped = ctypes.c_uint64(0)
+    rc = _native.batch_lib().k2h_amd_ralledata_dedup(
+        ctypes.c_void_p(blobs.data_ptr() or 1), blobs.numel(), _dev_ptr(blob_off), n,
+        _dev_ptr(consider) if consider is not None and n else None, ctypes.c_void_p(keep.data_ptr() or 1),
+        _dev_ptr(by) if want_by and n else None, ctypes.byref(dropped) if count else None, _stream_handle(stream))
+    _native.check(rc)
+    return keep, by, int(dropped.value) if count else None
+
+
+def route_ralledata(blobs, blob_off, hash_range: HashRange, std_fnv: bool = False, stream=None,
+                    dedup: bool = False):
     """What a receiver that owns `hash_range` does with a stream: check it, then keep the
     blobs that are OK and whose hash is in the target range (status == 0 and route & 1).
+    dedup: of those, also leave out the ones a later one supersedes (dedup_ralledata).
     Returns (Selected, CheckResult); the kept blobs feed k2h_set_element_by_binary."""
     torch = _torch()
     res = check_ralledata(blobs, blob_off, hash_range, std_fnv=std_fnv, stream=stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         keep = ((res.status == OK) & ((res.route & ROUTE_TARGET) != 0)).to(torch.uint8)
+    if dedup:
+        live, _by, _dropped = dedup_ralledata(blobs, blob_off, consider=keep, count=False, stream=stream)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            keep = keep & live
     return select_ralledata(blobs, blob_off, keep, stream=stream), res
