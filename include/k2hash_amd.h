@@ -308,6 +308,85 @@ int k2h_amd_ralledata_select(const void* blobs, uint64_t size, const uint64_t* b
 int k2h_amd_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
                             const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, void* stream);
 
+/* 4b''. A stream split into parts: the P-way sibling of k2h_amd_ralledata_select, a stable
+ * partition of variable-length blobs.  One call takes a stream and produces the same blobs
+ * grouped by part, in stream order within each part -- one buffer slice per owner node, or
+ * per lock domain of a loader -- where P calls of _select would read the stream's offsets
+ * and masks P times and synchronise P times.
+ *
+ * Device pointers: blobs, blob_off, part_ids, consider, out, out_off, index, part_out.  Host
+ * pointers: rule, part_first, part_byte; the last two have rule->parts + 1 entries each.
+ *
+ * Which blobs take part.  Blob i takes part when all of these hold:
+ *   - consider is NULL or consider[i] != 0;
+ *   - its span is valid as _select judges it: non-decreasing, ending at or before size;
+ *   - K2H_AMD_PART_IDS: part_ids[i] < parts, and its part is part_ids[i].  A blob of 0 bytes
+ *     with a valid span takes part, as in _select;
+ *   - K2H_AMD_PART_OWNER / _MASK: the span is at least 80 bytes.  The stored hash is the
+ *     blob's first 8 bytes; it is trusted, not recomputed, as SetElementByBinArray and _dedup
+ *     trust it (compose with _check through consider[i] = (status[i] == OK)).  Nothing of a
+ *     blob beyond those 8 bytes is read to decide its part, and nothing at all of a blob whose
+ *     span is bad or short.
+ *
+ * Outputs.
+ *   out        the participants of part 0 in stream order, then those of part 1, and so on,
+ *              back to back
+ *   out_off    (room for n + 1) kept + 1 offsets relative to out, starting at 0
+ *   index      (room for n; may be NULL) the original indices, in output order
+ *   part_out   (n entries; may be NULL) each blob's part, or K2H_AMD_PART_NONE if left out
+ *   part_first[p]  the rank in out_off at which part p starts; part_first[parts] = kept
+ *   part_byte[p]   the byte offset in out at which part p starts; part_byte[parts] = kept_bytes
+ * Part p is blobs [part_first[p], part_first[p+1]) of the output; an empty part has equal
+ * neighbours.  Because the partition is stable, all blobs of one identity (4b') land in one
+ * part in their original order: _dedup before or after the partition gives the same result.
+ *
+ * Flow, as _select: the counts first, one synchronisation of `stream` that returns part_first
+ * and part_byte, then the copy, asynchronous on `stream`.  out == NULL: counts only (and
+ * part_out if given).  kept_bytes > out_cap: K2H_AMD_EINVAL with both host arrays set and
+ * nothing written to out, out_off or index.  n == 0: K2H_AMD_OK, both host arrays zeroed, no
+ * device work.
+ *
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ * rule, part_first or part_byte NULL; an unknown kind; parts 0 or above K2H_AMD_PART_MAX; IDS
+ * without part_ids, or part_ids given with another kind; OWNER with max_hash == 0, span == 0 or
+ * parts != ceil(max_hash / span); blobs or blob_off NULL with n > 0; out given without out_off.
+ *
+ * OWNER.  part = (stored hash % max_hash) / span.  For every part p with p*span + span <=
+ * max_hash, the members are exactly the blobs whose route bit 0 is set by
+ * k2h_amd_ralledata_check with {target_hash = p*span, target_max_hash = max_hash,
+ * target_hash_range = span}.  The last, short part (when span does not divide max_hash) takes
+ * m = hash % max_hash in [p*span, max_hash); the reference's range would wrap there.  Parity
+ * with GetElementListToBinary is the same restatement as for _check.
+ *
+ * MASK.  part = (stored hash & mask) % parts.  With mask = collision_mask and parts <=
+ * collision_mask + 1, blobs in different parts have different hash & collision_mask
+ * (lib/k2hshm.cc:1093), so different CKINDEX entries -- the lock SetElementByBinArray takes
+ * (lib/k2hshmdirect.cc:369-373) -- in any table state.  A wider mask (cur_mask bits included)
+ * separates K_INDEX entries only when every K_INDEX at cur_mask is assigned; see the _table
+ * forms of section 3.  Whether feeding the parts from several threads actually speeds up
+ * libk2hash is NOT measured here: the library is not built by this project, and page
+ * allocation has locks of its own.
+ *
+ * Temporary device memory, kept per device between calls: per tile of 1024 blobs 16 * parts
+ * bytes (the tile's count and bytes per part, scanned in place), plus 2 bytes per blob for
+ * its part, plus the scan's own.  8 Mi blobs at 256 parts: 33.5 MB + 16.8 MB. */
+#define K2H_AMD_PART_MAX 256
+#define K2H_AMD_PART_NONE 0xFFFFFFFFu /* part_out[i] of a blob left out */
+#define K2H_AMD_PART_IDS 0            /* part[i] given by the caller */
+#define K2H_AMD_PART_OWNER 1          /* (stored hash % max_hash) / span */
+#define K2H_AMD_PART_MASK 2           /* (stored hash & mask) % parts */
+
+typedef struct k2h_amd_part_rule {
+  uint32_t kind, parts;    /* 1 <= parts <= K2H_AMD_PART_MAX */
+  uint64_t max_hash, span; /* OWNER: both > 0, parts == ceil(max_hash / span) */
+  uint64_t mask;           /* MASK */
+} k2h_amd_part_rule;
+
+int k2h_amd_ralledata_partition(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                                const k2h_amd_part_rule* rule, const uint32_t* part_ids, const uint8_t* consider,
+                                void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index, uint32_t* part_out,
+                                uint64_t* part_first, uint64_t* part_byte, void* stream);
+
 /* 4c. Blobs straight from scanned records: the middle of a bulk load whose file is already
  * in device memory.  The device scans of section 5 (k2h_amd_import_scan_device,
  * k2h_amd_archive_scan_device and their _scan_prehash_device forms) report every record as

@@ -44,6 +44,19 @@ class HashRange(ctypes.Structure):
 
 
 _rp = ctypes.POINTER(HashRange)
+
+K2H_AMD_PART_MAX = 256
+K2H_AMD_PART_NONE = 0xFFFFFFFF
+K2H_AMD_PART_IDS, K2H_AMD_PART_OWNER, K2H_AMD_PART_MASK = 0, 1, 2
+
+
+class PartRule(ctypes.Structure):
+    """k2h_amd_part_rule (include/k2hash_amd.h section 4b'')."""
+    _fields_ = [("kind", ctypes.c_uint32), ("parts", ctypes.c_uint32), ("max_hash", ctypes.c_uint64),
+                ("span", ctypes.c_uint64), ("mask", ctypes.c_uint64)]
+
+
+_prp = ctypes.POINTER(PartRule)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 
 # name -> (restype, argtypes); mirrors include/k2hash_amd.h
@@ -68,6 +81,8 @@ SIGNATURES = {
     "k2h_amd_ralledata_check": (ctypes.c_int, [_p, _u64, _p, _u64, _rp, ctypes.c_uint32, _p, _p, _p, _p, _p]),
     "k2h_amd_ralledata_select": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _p, _u64p, _u64p, _p]),
     "k2h_amd_ralledata_dedup": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _p]),
+    "k2h_amd_ralledata_partition": (ctypes.c_int, [_p, _u64, _p, _u64, _prp, _p, _p, _p, _u64, _p, _p, _p, _u64p,
+                                                   _u64p, _p]),
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_hash_ranges": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, ctypes.c_uint32, _p]),

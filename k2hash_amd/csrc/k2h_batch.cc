@@ -844,6 +844,41 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_dedup(const void* b
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_dedup", e);
 }
 
+// Section 4b'': the stream split into parts.  Judged on the host like the three above.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_partition(
+    const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const k2h_amd_part_rule* rule,
+    const uint32_t* part_ids, const uint8_t* consider, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
+    uint32_t* part_out, uint64_t* part_first, uint64_t* part_byte, void* stream) {
+  if (!rule) return fail(K2H_AMD_EINVAL, "ralledata_partition: NULL rule");
+  if (rule->kind != K2H_AMD_PART_IDS && rule->kind != K2H_AMD_PART_OWNER && rule->kind != K2H_AMD_PART_MASK)
+    return fail(K2H_AMD_EINVAL, "ralledata_partition: unknown rule kind");
+  if (rule->parts == 0 || rule->parts > K2H_AMD_PART_MAX)
+    return fail(K2H_AMD_EINVAL, "ralledata_partition: parts must be 1 .. K2H_AMD_PART_MAX (256)");
+  if (!part_first) return fail(K2H_AMD_EINVAL, "ralledata_partition: NULL part_first");
+  if (!part_byte) return fail(K2H_AMD_EINVAL, "ralledata_partition: NULL part_byte");
+  if (rule->kind == K2H_AMD_PART_IDS && !part_ids)
+    return fail(K2H_AMD_EINVAL, "ralledata_partition: K2H_AMD_PART_IDS needs part_ids");
+  if (rule->kind != K2H_AMD_PART_IDS && part_ids)
+    return fail(K2H_AMD_EINVAL, "ralledata_partition: part_ids given with a hash rule");
+  if (rule->kind == K2H_AMD_PART_OWNER) {
+    if (rule->max_hash == 0) return fail(K2H_AMD_EINVAL, "ralledata_partition: OWNER max_hash is 0");
+    if (rule->span == 0) return fail(K2H_AMD_EINVAL, "ralledata_partition: OWNER span is 0");
+    if ((rule->max_hash - 1) / rule->span + 1 != (uint64_t)rule->parts)
+      return fail(K2H_AMD_EINVAL, "ralledata_partition: OWNER parts is not ceil(max_hash / span)");
+  }
+  for (uint32_t p = 0; p <= rule->parts; ++p) part_first[p] = part_byte[p] = 0;
+  if (n == 0) return K2H_AMD_OK;
+  if (!blobs) return fail(K2H_AMD_EINVAL, "ralledata_partition: NULL blobs");
+  if (!blob_off) return fail(K2H_AMD_EINVAL, "ralledata_partition: NULL blob_off");
+  if (out && !out_off) return fail(K2H_AMD_EINVAL, "ralledata_partition: out given without out_off");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_ralledata_partition(blobs, size, blob_off, n, *rule, part_ids, consider, out, out_cap, out_off,
+                                           index, part_out, part_first, part_byte, (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EHIP || rc == K2H_AMD_ENOMEM) return fail(rc, "launch_ralledata_partition", e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "ralledata_partition: the kept blobs exceed out_cap, or too many blobs");
+}
+
 // ---------------------------------------------------------------------------
 // RALLEDATA blobs from range records (include/k2hash_amd.h section 4c).  Arguments are judged
 // before the device gate, so a bad call fails the same way with or without a GPU.

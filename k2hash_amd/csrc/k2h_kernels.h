@@ -131,6 +131,13 @@ int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blo
                            const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, hipStream_t stream,
                            hipError_t* herr);
 
+// A stream split into parts (k2h_ralledata_part.hip).  Returns a K2H_AMD_* code (the HIP error
+// in *herr) and synchronises the stream once.  n >= 1 and a rule the ABI has judged.
+int launch_ralledata_partition(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                               const k2h_amd_part_rule& rule, const uint32_t* part_ids, const uint8_t* consider,
+                               void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index, uint32_t* part_out,
+                               uint64_t* part_first, uint64_t* part_byte, hipStream_t stream, hipError_t* herr);
+
 // RALLEDATA blobs from range records (k2h_ralledata_recs.hip): the records of a scanned
 // import file (key + NUL, value + NUL) or archive (SCOM_SET_ALL records as stored) become
 // blobs packed in record order, a record that yields none taking 0 bytes; blob_off (n + 1,

@@ -277,6 +277,84 @@ def select_ralledata(blobs, blob_off, keep, out=None, count_only: bool = False, 
     return Selected(out[:kb], out_off[:k + 1], index[:k] if want_index else None, k, kb)
 
 
+PART_MAX = _native.K2H_AMD_PART_MAX
+PART_NONE = _native.K2H_AMD_PART_NONE  # part_of[i] of a blob left out (-1 as int32)
+
+
+class Partitioned(NamedTuple):
+    blobs: object      # uint8 tensor: part 0's blobs, then part 1's, ... (None when only counting)
+    blob_off: object   # int64 tensor, kept + 1, relative to `blobs`, from 0
+    index: object      # int64 tensor, kept: the blobs' indices in the input stream, in output order
+    part_of: object    # int32 tensor, n: each input blob's part, -1 (PART_NONE) if left out (want_parts)
+    part_first: list   # parts + 1 ints: part p is blobs [part_first[p], part_first[p + 1]) of the output
+    part_byte: list    # parts + 1 ints: and bytes [part_byte[p], part_byte[p + 1]) of `blobs`
+    kept: int
+    kept_bytes: int
+
+
+def partition_ralledata(blobs, blob_off, parts: int, *, ids=None, owner=None, mask=None, consider=None, out=None,
+                        count_only: bool = False, want_index: bool = True, want_parts: bool = False,
+                        stream=None) -> Partitioned:
+    """Group the blobs of a stream by part, in stream order within each part
+    (k2h_amd_ralledata_partition).  Exactly one rule is given: ids, an int32 tensor of n (a blob
+    with ids[i] outside [0, parts) is left out); owner=(max_hash, span), part = (stored hash %
+    max_hash) // span with parts == ceil(max_hash / span); or mask, part = (stored hash & mask) %
+    parts.  The hash rules trust the stored hash and leave out blobs shorter than a header.
+    consider: uint8 or bool tensor of n, the blobs that take part (None: all).  Without `out` the
+    kept bytes are counted first and an exact buffer is allocated (two calls, each synchronising
+    the stream once); an `out` too small for them raises with nothing written.  count_only: only
+    the counts and, with want_parts, part_of (blobs, blob_off and index are None)."""
+    torch = _torch()
+    n = _check_stream(blobs, blob_off, torch)
+    dev = blobs.device
+    if (ids is not None) + (owner is not None) + (mask is not None) != 1:
+        raise ValueError("exactly one of ids, owner and mask selects the rule")
+    if not 1 <= parts <= PART_MAX:
+        raise ValueError(f"parts must be 1 .. {PART_MAX}")
+    if ids is not None:
+        _check_dev(ids, "ids", torch.int32)
+        if ids.numel() != n or ids.device != dev:
+            raise ValueError("ids needs n entries on the blobs' device")
+        rule = _native.PartRule(_native.K2H_AMD_PART_IDS, parts, 0, 0, 0)
+    elif owner is not None:
+        rule = _native.PartRule(_native.K2H_AMD_PART_OWNER, parts, int(owner[0]), int(owner[1]), 0)
+    else:
+        rule = _native.PartRule(_native.K2H_AMD_PART_MASK, parts, 0, 0, int(mask))
+    if consider is not None:
+        if consider.dtype == torch.bool:
+            consider = consider.view(torch.uint8)
+        _check_dev(consider, "consider", torch.uint8)
+        if consider.numel() != n or consider.device != dev:
+            raise ValueError("consider needs n entries on the blobs' device")
+    lib = _native.batch_lib()
+    first, byte = (ctypes.c_uint64 * (parts + 1))(), (ctypes.c_uint64 * (parts + 1))()
+    part_of = torch.empty(n, dtype=torch.int32, device=dev) if want_parts else None
+    opt = lambda t: ctypes.c_void_p(t.data_ptr() or 1) if t is not None else None  # noqa: E731
+
+    def call(o, cap, ooff, idx, pout):
+        return lib.k2h_amd_ralledata_partition(
+            ctypes.c_void_p(blobs.data_ptr() or 1), blobs.numel(), _dev_ptr(blob_off), n, ctypes.byref(rule),
+            opt(ids), opt(consider), o, cap, ooff, idx, pout, first, byte, _stream_handle(stream))
+    if count_only or out is None:
+        _native.check(call(None, 0, None, None, opt(part_of)))
+        if count_only:
+            return Partitioned(None, None, None, part_of, list(first), list(byte), int(first[parts]),
+                               int(byte[parts]))
+        out = torch.empty(max(int(byte[parts]), 1), dtype=torch.uint8, device=dev)
+    else:
+        _check_dev(out, "out", torch.uint8)
+        if out.device != dev:
+            raise ValueError("out is on another device than the blobs")
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    index = torch.empty(n, dtype=torch.int64, device=dev) if want_index else None
+    _native.check(call(_dev_ptr(out), out.numel(), _dev_ptr(out_off), opt(index), opt(part_of)))
+    k, kb = int(first[parts]), int(byte[parts])
+    if n == 0:
+        out_off[:1] = 0
+    return Partitioned(out[:kb], out_off[:k + 1], index[:k] if want_index else None, part_of, list(first), list(byte),
+                       k, kb)
+
+
 NO_LATER = (1 << 64) - 1  # by[i] of dedup_ralledata when no later blob has blob i's identity (-1 as int64)
 
 
