@@ -448,6 +448,71 @@ int k2h_amd_archive_ralledata(const void* file, uint64_t size, const struct k2h_
                               void* out, uint64_t out_cap, uint64_t* blob_off, uint64_t* total, uint32_t flags,
                               void* stream);
 
+/* 4d. A stream written as a k2hash archive: the portable exit of a blob stream.  Blobs fit
+ * only a table with the hash function and seed that produced their hash fields; an archive
+ * stores no hashes (K2HArchive::Load, lib/k2harchive.cc:279-383, re-hashes every key through
+ * ReplaceAll), so k2h_load_archive and the load command of k2hlinetool replay it into any
+ * table.  K2HArchive::Save (lib/k2harchive.cc:86-257) writes one SCOM_SET_ALL record per
+ * element; this call writes the same record for every participating blob, on the device.
+ *
+ * blobs, blob_off, keep, out and rec_off are device pointers (the stream arguments mean what
+ * they mean for k2h_amd_ralledata_check); records and total are host pointers.  keep and
+ * records may be NULL; total is required.
+ *
+ * Participants, the rule of _dedup.  Blob i yields a record when keep is NULL or keep[i] != 0,
+ * its span is good (not BAD_SPAN) and its header passes the header tests of
+ * k2h_amd_ralledata_check (not EMPTY, NO_KEY or BAD_RANGE).  The hash and subhash fields are
+ * neither read for a decision nor verified: the archive does not store them.  A blob with a
+ * key and nothing else takes part (K2HCommandArchive::Put accepts it, lib/k2hcommand.cc:71).
+ *
+ * The record is what K2HCommandArchive::SetAll produces for the blob's four segments
+ * (lib/k2hcommand.cc:69-135, scom_init at lib/k2hcommand.h:99-113), a packed 104-byte SCOM
+ * header (the layout of section 5) and the data:
+ *   szCommand      "\nK2H_SET_ALL" followed by four 0x00 bytes
+ *   type           0 (SCOM_SET_ALL)
+ *   key_length, val_length, skey_length, attr_length   the blob's four lengths
+ *   exdata_length  0
+ *   key_pos = 104, val_pos = 104 + key_length, skey_pos = val_pos + val_length,
+ *   attrs_pos = skey_pos + skey_length
+ *   exdata_pos     104 (scom_init sets it and Put leaves it for SET_ALL)
+ *   then the key, value, subkeys and attrs bytes, in that order and back to back.
+ * The segment bytes are read from the blob at its *_pos fields, wherever they point inside
+ * the blob: order, overlap and slack in the blob are not assumptions, and the pos of a
+ * length-0 segment is ignored.  One SET_ALL record is written however large the value is:
+ * Save splits a value above 10 MiB into SCOM_OW_VAL records, but Load has no such limit.
+ *
+ * Output and flow, the convention of section 4c.  Records are packed back to back in blob
+ * order: the record of blob i is out[rec_off[i], rec_off[i+1]), and a blob that yields none
+ * has 0 bytes there.  rec_off has n+1 entries and is required for n > 0; rec_off[0] = 0,
+ * *total = rec_off[n], *records = the number of blobs that yielded a record.  out[0, *total)
+ * is a file K2HArchive::Load and k2h_amd_archive_scan walk from offset 0.  A sizing kernel
+ * and an exclusive sum fill rec_off, `stream` is synchronised once to return the counts, then
+ * the records are built asynchronously on `stream`.  out == NULL: sizes and counts only.
+ * *total > out_cap: K2H_AMD_EINVAL with *total, *records and rec_off set and nothing written
+ * to out.  n == 0: K2H_AMD_OK, *total = 0, *records = 0, rec_off[0] = 0 if rec_off is given,
+ * no other device work.
+ *
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own
+ * message: total NULL; rec_off, blobs or blob_off NULL with n > 0; n so large that
+ * n * (104 + 4 * size) overflows 64 bits.
+ *
+ * No byte outside [0, size) of the stream is read except within the aligned 16 bytes that
+ * hold a valid byte.  Nothing of a blob whose span is bad or whose keep byte is 0 is read,
+ * and nothing beyond the header of any other blob that yields no record -- except, for both,
+ * within the aligned 16 bytes they share with a participant.  Nothing outside out[0, *total)
+ * and rec_off[0..n] is written;
+ * bytes that share an aligned 16-byte piece with the first or last output byte keep their
+ * value.  All absolute offsets are 64-bit.
+ *
+ * Parity: the record layout is pinned by the SET_ALL records the reference's own
+ * K2HCommandArchive wrote into the archive fixture of oracle/gen_archive.cc.  That
+ * K2HArchive::Load accepts the output is a restatement: libk2hash itself is not built by
+ * this project's tests. */
+#define K2H_AMD_SCOM_HEADER 104 /* sizeof(SCOM), packed (lib/k2hcommand.h:69-82) */
+int k2h_amd_ralledata_archive(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                              const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* rec_off,
+                              uint64_t* records, uint64_t* total, void* stream);
+
 /* ---------------------------------------------------------------------------
  * 5. Bulk key streams: keys anywhere in a buffer, and k2hash archives.
  *

@@ -22,6 +22,7 @@ K2H_AMD_ENODEV = -4
 K2H_AMD_FLAG_STD_FNV = 0x1
 K2H_AMD_FLAG_CSTR = 0x2
 K2H_AMD_IMPORT_TSV, K2H_AMD_IMPORT_MDBM = 0, 1
+K2H_AMD_SCOM_HEADER = 104
 
 _u64 = ctypes.c_uint64
 _p = ctypes.c_void_p
@@ -85,6 +86,7 @@ SIGNATURES = {
                                                    _u64p, _p]),
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
+    "k2h_amd_ralledata_archive": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64p, _u64p, _p]),
     "k2h_amd_hash_ranges": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_scan": (ctypes.c_int, [_p, _u64, _p, _u64, _p]),
     "k2h_amd_archive_prehash_host": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, ctypes.c_uint32, ctypes.c_int]),

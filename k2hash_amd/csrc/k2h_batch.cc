@@ -942,6 +942,38 @@ __attribute__((visibility("default"))) int k2h_amd_archive_ralledata(const void*
   return rc == K2H_AMD_OK ? rc : fail(rc, "archive_ralledata: the blobs exceed out_cap, or too many records");
 }
 
+// ---------------------------------------------------------------------------
+// A blob stream written as a k2hash archive (include/k2hash_amd.h section 4d).  Arguments are
+// judged before the device gate, so a bad call fails the same way with or without a GPU.
+// ---------------------------------------------------------------------------
+__attribute__((visibility("default"))) int k2h_amd_ralledata_archive(const void* blobs, uint64_t size,
+                                                                     const uint64_t* blob_off, uint64_t n,
+                                                                     const uint8_t* keep, void* out, uint64_t out_cap,
+                                                                     uint64_t* rec_off, uint64_t* records,
+                                                                     uint64_t* total, void* stream) {
+  if (!total) return fail(K2H_AMD_EINVAL, "ralledata_archive: NULL total");
+  *total = 0;
+  if (records) *records = 0;
+  if (n == 0) {
+    if (!rec_off) return K2H_AMD_OK;
+    K2H_GATE();
+    hipError_t e = hipMemsetAsync(rec_off, 0, 8, (hipStream_t)stream);
+    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_archive", e);
+  }
+  if (!rec_off) return fail(K2H_AMD_EINVAL, "ralledata_archive: NULL rec_off");
+  if (!blobs) return fail(K2H_AMD_EINVAL, "ralledata_archive: NULL blobs");
+  if (!blob_off) return fail(K2H_AMD_EINVAL, "ralledata_archive: NULL blob_off");
+  // a record is at most 104 + 4 size bytes (each of a blob's four segments lies inside it)
+  if (size > (~0ull - K2H_AMD_SCOM_HEADER) / 4 || n > ~0ull / (K2H_AMD_SCOM_HEADER + 4 * size))
+    return fail(K2H_AMD_EINVAL, "ralledata_archive: n records of this stream overflow 64 bits");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_ralledata_archive(blobs, size, blob_off, n, keep, out, out_cap, rec_off, records, total,
+                                         (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EHIP) return fail(rc, "launch_ralledata_archive", e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "ralledata_archive: the records exceed out_cap, or too many blobs");
+}
+
 __attribute__((visibility("default"))) const char* k2h_amd_version(void) {
   return "k2hash_amd 0.1 (FNV-1A BUILTIN, gfx950 HIP batch kernels)";
 }

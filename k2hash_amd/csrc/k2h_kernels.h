@@ -151,6 +151,15 @@ int launch_archive_ralledata(const void* file, uint64_t size, const k2h_amd_arch
                              uint64_t seed, void* out, uint64_t out_cap, uint64_t* blob_off, uint64_t* total,
                              hipStream_t stream, hipError_t* herr);
 
+// A blob stream as a k2hash archive (k2h_ralledata_archive.hip): one SCOM_SET_ALL record per
+// participating blob, packed in blob order; rec_off (n + 1, required) by a sizing kernel and an
+// exclusive sum.  Returns a K2H_AMD_* code (the HIP error in *herr) and synchronises the stream
+// once to return *total and *records (may be NULL); out == NULL: sizes only; *total > out_cap:
+// K2H_AMD_EINVAL with nothing written to out.  n >= 1.
+int launch_ralledata_archive(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                             const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* rec_off, uint64_t* records,
+                             uint64_t* total, hipStream_t stream, hipError_t* herr);
+
 // Keys at arbitrary (start, length) ranges (k2h_ranges.hip); cstr: hash key + NUL.
 hipError_t launch_ranges(const void* base, const uint64_t* starts, const uint64_t* lens, uint64_t n, uint64_t seed,
                          bool cstr, uint64_t* h1, uint64_t* h2, hipStream_t stream);

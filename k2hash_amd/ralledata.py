@@ -2,7 +2,8 @@
 hashes, built on the GPU (include/k2hash_amd.h section 4), and the consumer side: a blob
 stream checked, routed by hash range and compacted on the GPU (section 4b); and the hop
 between the device scans and those two: blobs built straight from the range records of a
-scanned import file or archive (section 4c).
+scanned import file or archive (section 4c); and a stream's portable exit, the same elements
+written as a k2hash archive that loads into a table of any seed (section 4d).
 
 A blob is what K2HShm::GetElementToBinary writes (lib/k2hshmdirect.cc:59-88) on the
 packed struct of lib/k2hshmdirect.h:36-47, and what k2h_set_element_by_binary
@@ -353,6 +354,67 @@ def partition_ralledata(blobs, blob_off, parts: int, *, ids=None, owner=None, ma
         out_off[:1] = 0
     return Partitioned(out[:kb], out_off[:k + 1], index[:k] if want_index else None, part_of, list(first), list(byte),
                        k, kb)
+
+
+SCOM_HEADER = _native.K2H_AMD_SCOM_HEADER  # sizeof(SCOM): the header of an archive record
+
+
+class Archived(NamedTuple):
+    bytes: object    # uint8 tensor: the SET_ALL records back to back, a k2hash archive (None when only counting)
+    rec_off: object  # int64 tensor, n + 1: blob i's record is bytes[rec_off[i]:rec_off[i + 1]] (0 bytes: none)
+    records: int     # the blobs that yielded a record
+    total: int       # rec_off[n]
+
+
+def ralledata_to_archive(blobs, blob_off, keep=None, out=None, count_only: bool = False, stream=None) -> Archived:
+    """Write a blob stream as a k2hash archive on the device (k2h_amd_ralledata_archive): one
+    SCOM_SET_ALL record, as K2HArchive::Save writes it, for every blob with keep[i] != 0 (None:
+    all), a good span and a header that is not EMPTY, NO_KEY or BAD_RANGE; the stored hashes are
+    not looked at, and the result loads into a table of any hash function (k2h_load_archive).
+    keep: uint8 or bool tensor of n.  Without `out` the records are sized first and an exact
+    buffer is allocated (two calls, each synchronising the stream once); an `out` too small for
+    them raises with nothing written.  count_only: only rec_off and the counts (bytes is None).
+    A value above 10 MiB still becomes one SET_ALL record (Save would split it; Load does not
+    mind)."""
+    torch = _torch()
+    n = _check_stream(blobs, blob_off, torch)
+    dev = blobs.device
+    if keep is not None:
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        _check_dev(keep, "keep", torch.uint8)
+        if keep.numel() != n or keep.device != dev:
+            raise ValueError("keep needs n entries on the blobs' device")
+    lib = _native.batch_lib()
+    rec_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    records, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(o, cap):
+        _native.check(lib.k2h_amd_ralledata_archive(
+            ctypes.c_void_p(blobs.data_ptr() or 1), blobs.numel(), _dev_ptr(blob_off), n,
+            _dev_ptr(keep) if keep is not None and n else None, o, cap, _dev_ptr(rec_off), ctypes.byref(records),
+            ctypes.byref(total), _stream_handle(stream)))
+    if count_only or out is None:
+        call(None, 0)  # sizes only
+        if count_only:
+            return Archived(None, rec_off, int(records.value), int(total.value))
+        out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=dev)
+        if not total.value:
+            return Archived(out[:0], rec_off, 0, 0)
+    else:
+        _check_dev(out, "out", torch.uint8)
+        if out.device != dev:
+            raise ValueError("out is on another device than the blobs")
+    call(_dev_ptr(out), out.numel())
+    return Archived(out[:int(total.value)], rec_off, int(records.value), int(total.value))
+
+
+def import_file_to_archive(file, fmt: str = "tsv", stream=None) -> Archived:
+    """import_file_to_ralledata, then ralledata_to_archive: a TSV or mdbm_export file in device
+    memory converted to k2hash's other bulk format.  Every line becomes the SET_ALL record of
+    key + NUL and value + NUL that K2HArchive::Save writes after k2himport's Set."""
+    blobs, blob_off = import_file_to_ralledata(file, fmt, stream=stream)
+    return ralledata_to_archive(blobs, blob_off, stream=stream)
 
 
 NO_LATER = (1 << 64) - 1  # by[i] of dedup_ralledata when no later blob has blob i's identity (-1 as int64)
