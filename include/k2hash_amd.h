@@ -387,6 +387,103 @@ int k2h_amd_ralledata_partition(const void* blobs, uint64_t size, const uint64_t
                                 void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index, uint32_t* part_out,
                                 uint64_t* part_first, uint64_t* part_byte, void* stream);
 
+/* 4b''''. The times inside a blob's attrs: the mtime window of GetElementListToBinary, and a
+ * dedup that works on streams whose blobs carry the builtin mtime.  Both rest on one device
+ * walk of the serialized K2HAttrs (k2hash_amd/csrc/k2h_ralle_attrs.h).
+ *
+ * Parsing, K2HAttrs::Serialize(const unsigned char*, size_t), lib/k2hattrs.cc:121-166.  A is
+ * the attrs segment, AL its length.  AL < 8: no entries.  Else count = the u64 at 0, pos = 8,
+ * rest = AL - 8, and up to count times: rest < 16 stops; kl, vl = the u64s at pos, pos + 8; an
+ * entry that does not fit in rest stops (the entries accepted before stay); the key is
+ * A[pos + 16, + kl) and the value the vl bytes behind it; kl == 0 is consumed but not kept
+ * (insert refuses it); a key equal to an earlier one replaces it (:356-363); pos += 16 + kl +
+ * vl.  One departure: the reference forms 16 + kl + vl in size_t, and where that sum wraps it
+ * reads out of bounds; here kl > rest - 16 || vl > rest - 16 - kl is tested without forming
+ * the sum, and the walk stops.
+ *
+ * Times, K2hAttrBuiltin::GetTime, lib/k2hattrbuiltin.cc:864-883.  A time is present exactly
+ * when the last accepted entry with its key has vl == 16; the key is "mtime\0" (kl 6) or
+ * "expire\0" (kl 7), the NUL included as find(const char*) includes it; the value is a struct
+ * timespec, int64 tv_sec then int64 tv_nsec.  Times compare signed, sec first, nsec as stored.
+ * A later entry of the same key with vl != 16 hides an earlier good one.  Expired at `now`
+ * (IsExpire, :830-862; the reference reads the clock, here the caller passes it): expire is
+ * present and expire < now.
+ *
+ * k2h_amd_ralledata_times (async on `stream`; device pointers except `window`, a host pointer
+ * that may be NULL and is read before the call returns).
+ *
+ * Participants, as _dedup: consider is NULL or consider[i] != 0, the span is good and the
+ * header is not EMPTY, NO_KEY or BAD_RANGE.  A non-participant gets tflags 0, zero times and
+ * keep 0, and nothing of it beyond its header is read.
+ *
+ *   tflags[i]  K2H_AMD_TIMES_MTIME / _EXPIRE: that time is present; _CUT: the walk stopped
+ *              before count entries were read, or AL is 1 to 7; _ATTRS: attrs_length != 0
+ *   mtime, expire  (2 n int64 each) sec, nsec of blob i at [2 i], [2 i + 1]; an absent time
+ *              is 0, 0
+ *   keep[i]    for a participant, lib/k2hshmdirect.cc:137-197 in its order: 0 if WIN_EXPIRE is
+ *              set and the blob is expired at window->now; otherwise, if the blob has an mtime,
+ *              0 if need_start(i) and WIN_START is set and mtime < start, otherwise 0 if
+ *              WIN_END is set and end < mtime, otherwise 1; a blob without mtime is 1
+ *              (:155-157).  need_start(i) = (route[i] & K2H_AMD_ROUTE_OLD) != 0, the bit
+ *              k2h_amd_ralledata_check computes; route == NULL: true for every blob.
+ *              window == NULL: keep[i] = participant.  Route bit 0 is not looked at: the
+ *              caller ANDs it in.
+ * Each of the four may be NULL, but not all.  K2H_AMD_EINVAL, judged on the host before any
+ * device is touched, each with its own message: all four outputs NULL; route given without
+ * window; unknown window flag bits; blobs or blob_off NULL with n > 0.  n == 0: K2H_AMD_OK, no
+ * device work.
+ *
+ * No byte outside [0, size) is read except within the aligned 16 bytes that hold a valid
+ * byte; every load of the walk lies inside the attrs segment, at any alignment.  One lane
+ * walks one segment, a chain of one dependent 16-byte load per entry.  Dropping blobs because
+ * they are themselves expired is not done anywhere: an expired blob still overwrites and
+ * hides an older element; _times reports the fact and the policy is the caller's.
+ *
+ * k2h_amd_ralledata_dedup_mtime: the arguments of k2h_amd_ralledata_dedup plus pts, a required
+ * host pointer (read before the call returns): the pts the caller will pass to
+ * k2h_set_element_by_binary for every blob of the stream.  Identity, participants, by, dropped
+ * and the async / sync rule are those of _dedup.  Blob i is superseded by the nearest later
+ * participant j of its identity when
+ *   (a) i has no mtime (no attrs, or attrs in which GetMTime fails), or
+ *   (b) i and j both have an mtime, m_i < m_j and m_i < pts (both strict; they mirror the <=
+ *       refusals at lib/k2hshmdirect.cc:402 and :416).
+ * Otherwise i is kept: i with an mtime before a j without one is kept, and an expired i gets
+ * no special treatment.  Against a prior element E, i either is refused exactly when j would
+ * be, or is accepted and then overwritten by j.  (a), E without mtime, without attrs or
+ * expired: j overwrites i because i has no mtime (:395-400); (a), E live with an mtime: both
+ * are refused (:421-427); (b), i accepted: j is accepted because pts > m_i and m_j > m_i; (b),
+ * i refused (pts <= m_E, or m_i <= m_E against a live E): the stream without i meets the same
+ * E.  Three assumptions: one pts for the whole feed; the blobs are fed in stream order; an
+ * element that is expired stays expired.  Every blob _dedup drops is dropped here too, and on
+ * a stream without attrs the two results are equal.  Temporary device memory: that of _dedup
+ * plus 16 bytes per blob.  K2H_AMD_EINVAL as _dedup, and for pts NULL (with n > 0).
+ *
+ * Parity: the parse is pinned by tests/golden/ralle_attrs.json, written by the reference's own
+ * K2HAttrs (tests/golden/gen_ralle_attrs.cc); GetTime, IsExpire, the window and the replay that
+ * shows the drop rule sound are restatements -- libk2hash itself is not built by this
+ * project's tests. */
+typedef struct k2h_amd_timespec {
+  int64_t sec, nsec;
+} k2h_amd_timespec;
+#define K2H_AMD_WIN_START 0x1u
+#define K2H_AMD_WIN_END 0x2u
+#define K2H_AMD_WIN_EXPIRE 0x4u
+typedef struct k2h_amd_time_window {
+  uint32_t flags, reserved;
+  k2h_amd_timespec start, end, now;
+} k2h_amd_time_window;
+#define K2H_AMD_TIMES_MTIME 0x1u
+#define K2H_AMD_TIMES_EXPIRE 0x2u
+#define K2H_AMD_TIMES_CUT 0x4u
+#define K2H_AMD_TIMES_ATTRS 0x8u /* attrs_length != 0 */
+
+int k2h_amd_ralledata_times(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                            const uint8_t* consider, const k2h_amd_time_window* window, const uint8_t* route,
+                            uint8_t* tflags, int64_t* mtime, int64_t* expire, uint8_t* keep, void* stream);
+int k2h_amd_ralledata_dedup_mtime(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                                  const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped,
+                                  const k2h_amd_timespec* pts, void* stream);
+
 /* 4c. Blobs straight from scanned records: the middle of a bulk load whose file is already
  * in device memory.  The device scans of section 5 (k2h_amd_import_scan_device,
  * k2h_amd_archive_scan_device and their _scan_prehash_device forms) report every record as

@@ -18,8 +18,8 @@ from .hashfunc import (K2H_2ND_HASH_FUNC, K2H_HASH_FUNC, K2H_HASH_VER_FUNC, K2Ha
                        k2h_hash_version, k2h_second_hash)
 from .batch import (bucket_index, hash_csr, hash_csr_host, hash_csr_index, hash_fixed, hash_fixed_host,
                     hash_fixed_index, synth_bytes, synth_offsets, unpack_kindex, version)
-from .ralledata import (HashRange, archive_to_ralledata, check_ralledata, dedup_ralledata, import_file_to_archive,
-                        import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
+from .ralledata import (HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
+                        dedup_ralledata, import_file_to_archive, import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
                         ralledata_to_archive, route_ralledata, select_ralledata)
 
 __all__ = [
@@ -29,4 +29,5 @@ __all__ = [
     "hash_csr_index", "unpack_kindex", "check_ralledata", "select_ralledata", "route_ralledata", "HashRange",
     "make_hash_range", "import_to_ralledata", "archive_to_ralledata", "import_file_to_ralledata",
     "dedup_ralledata", "partition_ralledata", "ralledata_to_archive", "import_file_to_archive",
+    "blob_times", "TimeWindow", "Times",
 ]

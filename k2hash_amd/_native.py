@@ -60,6 +60,24 @@ class PartRule(ctypes.Structure):
 _prp = ctypes.POINTER(PartRule)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 
+K2H_AMD_WIN_START, K2H_AMD_WIN_END, K2H_AMD_WIN_EXPIRE = 1, 2, 4
+K2H_AMD_TIMES_MTIME, K2H_AMD_TIMES_EXPIRE, K2H_AMD_TIMES_CUT, K2H_AMD_TIMES_ATTRS = 1, 2, 4, 8
+
+
+class Timespec(ctypes.Structure):
+    """k2h_amd_timespec (include/k2hash_amd.h section 4b'''')."""
+    _fields_ = [("sec", ctypes.c_int64), ("nsec", ctypes.c_int64)]
+
+
+class TimeWindowStruct(ctypes.Structure):
+    """k2h_amd_time_window (include/k2hash_amd.h section 4b'''')."""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("start", Timespec), ("end", Timespec),
+                ("now", Timespec)]
+
+
+_twp = ctypes.POINTER(TimeWindowStruct)
+_tsp = ctypes.POINTER(Timespec)
+
 # name -> (restype, argtypes); mirrors include/k2hash_amd.h
 SIGNATURES = {
     "k2h_hash": (_u64, [_p, ctypes.c_size_t]),
@@ -82,6 +100,8 @@ SIGNATURES = {
     "k2h_amd_ralledata_check": (ctypes.c_int, [_p, _u64, _p, _u64, _rp, ctypes.c_uint32, _p, _p, _p, _p, _p]),
     "k2h_amd_ralledata_select": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _p, _u64p, _u64p, _p]),
     "k2h_amd_ralledata_dedup": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _p]),
+    "k2h_amd_ralledata_times": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _twp, _p, _p, _p, _p, _p, _p]),
+    "k2h_amd_ralledata_dedup_mtime": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _tsp, _p]),
     "k2h_amd_ralledata_partition": (ctypes.c_int, [_p, _u64, _p, _u64, _prp, _p, _p, _p, _u64, _p, _p, _p, _u64p,
                                                    _u64p, _p]),
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),

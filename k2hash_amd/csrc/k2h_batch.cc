@@ -844,6 +844,45 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_dedup(const void* b
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_dedup", e);
 }
 
+// Section 4b'''': the times in the blobs' attrs.  Judged on the host like the ones above.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_times(
+    const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const uint8_t* consider,
+    const k2h_amd_time_window* window, const uint8_t* route, uint8_t* tflags, int64_t* mtime, int64_t* expire,
+    uint8_t* keep, void* stream) {
+  if (!tflags && !mtime && !expire && !keep)
+    return fail(K2H_AMD_EINVAL, "ralledata_times: tflags, mtime, expire and keep are all NULL");
+  if (route && !window) return fail(K2H_AMD_EINVAL, "ralledata_times: route given without window");
+  if (window && (window->flags & ~(K2H_AMD_WIN_START | K2H_AMD_WIN_END | K2H_AMD_WIN_EXPIRE)))
+    return fail(K2H_AMD_EINVAL, "ralledata_times: unknown window flag bits");
+  if (n == 0) return K2H_AMD_OK;
+  if (!blobs) return fail(K2H_AMD_EINVAL, "ralledata_times: NULL blobs");
+  if (!blob_off) return fail(K2H_AMD_EINVAL, "ralledata_times: NULL blob_off");
+  K2H_GATE();
+  hipError_t e = k2h::launch_ralledata_times(blobs, size, blob_off, n, consider, window, route, tflags, mtime, expire,
+                                             keep, (hipStream_t)stream);
+  return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "launch_ralledata_times", e);
+}
+
+// And the dedup under the mtime rule.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_dedup_mtime(
+    const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const uint8_t* consider, uint8_t* keep,
+    uint64_t* by, uint64_t* dropped, const k2h_amd_timespec* pts, void* stream) {
+  if (dropped) *dropped = 0;
+  if (n == 0) return K2H_AMD_OK;
+  if (!keep) return fail(K2H_AMD_EINVAL, "ralledata_dedup_mtime: NULL keep");
+  if (!blobs) return fail(K2H_AMD_EINVAL, "ralledata_dedup_mtime: NULL blobs");
+  if (!blob_off) return fail(K2H_AMD_EINVAL, "ralledata_dedup_mtime: NULL blob_off");
+  if (!pts) return fail(K2H_AMD_EINVAL, "ralledata_dedup_mtime: NULL pts");
+  if (n > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL,
+                "ralledata_dedup_mtime: more than 2^32 - 2 blobs (indices are sorted as 32-bit values)");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_ralledata_dedup_mtime(blobs, size, blob_off, n, consider, pts, keep, by, dropped,
+                                             (hipStream_t)stream, &e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_dedup_mtime", e);
+}
+
 // Section 4b'': the stream split into parts.  Judged on the host like the three above.
 __attribute__((visibility("default"))) int k2h_amd_ralledata_partition(
     const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const k2h_amd_part_rule* rule,

@@ -130,6 +130,17 @@ int launch_ralledata_select(const void* blobs, uint64_t size, const uint64_t* bl
 int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
                            const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, hipStream_t stream,
                            hipError_t* herr);
+// The same under the mtime rule; pts is a host pointer, read before the call returns.
+int launch_ralledata_dedup_mtime(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                                 const uint8_t* consider, const k2h_amd_timespec* pts, uint8_t* keep, uint64_t* by,
+                                 uint64_t* dropped, hipStream_t stream, hipError_t* herr);
+
+// The mtime and expire of every blob's attrs and the time-window selection
+// (k2h_ralledata_times.hip).  Asynchronous on the stream; n >= 1, window may be NULL.
+hipError_t launch_ralledata_times(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                                  const uint8_t* consider, const k2h_amd_time_window* window, const uint8_t* route,
+                                  uint8_t* tflags, int64_t* mtime, int64_t* expire, uint8_t* keep,
+                                  hipStream_t stream);
 
 // A stream split into parts (k2h_ralledata_part.hip).  Returns a K2H_AMD_* code (the HIP error
 // in *herr) and synchronises the stream once.  n >= 1 and a rule the ABI has judged.

@@ -11,6 +11,13 @@
 // exactly as j does (:402-405, :421-427).  A blob with attrs is never dropped and never
 // causes a drop.
 //
+// k2h_amd_ralledata_dedup_mtime (section 4b'''') runs the same three stages with another drop
+// rule, for streams whose blobs carry the builtin mtime: its gather also walks the attrs of
+// the participants that have some (k2h_ralle_attrs.h) and leaves each mtime for resolve, where
+// i is superseded by j when i has no mtime, or both have one and m_i < m_j and m_i < pts.
+// The kernels are templates on that bool; the plain rule's instantiations are the code they
+// were.
+//
 // Three stages, all on the caller's stream:
 //   gather   one lane per blob: span, header and classify (k2h_ralle_header.h, shared with
 //            the check kernel); a participant leaves its stored hash and a 32-byte side
@@ -44,6 +51,7 @@
 
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
+#include "k2h_ralle_attrs.h"
 #include "k2h_ralle_header.h"
 
 namespace k2h {
@@ -63,12 +71,27 @@ struct __attribute__((aligned(16))) Side {
 };
 static_assert(sizeof(Side) == 32, "two 16-byte loads");
 
+// The mtime rule (k2h_amd_ralledata_dedup_mtime) keeps a participant's mtime next to its side
+// record, in an array of its own so that the side record and the plain rule's kernels stay what
+// they are.  A blob without attrs, or whose attrs give no mtime (GetMTime fails), has none.
+struct __attribute__((aligned(16))) Mtime {
+  int64_t sec, nsec;
+};
+struct MtimeRule {
+  Mtime* mt;          // n entries; entry i is written only for a blob with kHasMtime
+  int64_t sec, nsec;  // pts
+};
+constexpr uint64_t kHasMtime = 2;  // Side::attrs bit 1, set by the gather of the mtime rule only
+
 // keep[i] = 1 for a participant (resolve clears the superseded ones), by[i] = ~0; the
 // participant's stored hash to hash[i] and its side record to side[i]; the tile's count.
+// MT: a participant with attrs also has them walked (k2h_ralle_attrs.h) and leaves its mtime.
+template <bool MT>
 __global__ __launch_bounds__(256) void ralledata_dedup_gather_kernel(
     const uint8_t* __restrict__ blobs, uint64_t size, const uint64_t* __restrict__ off, uint64_t n,
     const uint8_t* __restrict__ consider, uint8_t* __restrict__ keep, uint64_t* __restrict__ by,
-    uint64_t* __restrict__ hash, Side* __restrict__ side, uint64_t* __restrict__ tile_count) {
+    uint64_t* __restrict__ hash, Side* __restrict__ side, uint64_t* __restrict__ tile_count,
+    Mtime* __restrict__ mt) {
   typedef hipcub::BlockReduce<uint32_t, kDedupBlobs> Reduce;
   __shared__ typename Reduce::TempStorage tmp;
   const uint64_t i = (uint64_t)blockIdx.x * kDedupBlobs + threadIdx.x;
@@ -81,7 +104,19 @@ __global__ __launch_bounds__(256) void ralledata_dedup_gather_kernel(
       if (classify(f, e - b) == K2H_AMD_RALLE_OK) {
         part = 1;
         hash[i] = f[0];
-        side[i] = Side{f[1], b + f[6], f[2], f[5] ? 1ull : 0ull};
+        if constexpr (MT) {
+          uint64_t attrs = f[5] ? 1ull : 0ull;
+          if (f[5]) {
+            const AttrTimes t = walk_attrs(blobs + b + f[9], f[5]);
+            if (t.flags & kAttrMtime) {
+              attrs |= kHasMtime;
+              mt[i] = Mtime{t.msec, t.mnsec};
+            }
+          }
+          side[i] = Side{f[1], b + f[6], f[2], attrs};
+        } else {
+          side[i] = Side{f[1], b + f[6], f[2], f[5] ? 1ull : 0ull};
+        }
       }
     }
   }
@@ -132,11 +167,13 @@ __device__ __forceinline__ bool same_key(const uint8_t* a, const uint8_t* b, uin
 // keys / idx: the pairs, sorted by the hash bits under `mask` (sort_bits_for).  Writes
 // keep[i] = 0 for a superseded blob and by[i] for every blob that has a later one of its
 // identity; counts the superseded into the kCounters words of `dropped` (their sum is the
-// count).
+// count).  MT: the mtime rule in place of the attrs rule -- i is superseded by j when i has
+// no mtime, or both have one and m_i < m_j and m_i < pts (both strict).
+template <bool MT>
 __global__ __launch_bounds__(kResolveBlock) void ralledata_dedup_resolve_kernel(
     const uint8_t* __restrict__ blobs, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
     uint64_t n, uint64_t mask, const Side* __restrict__ side, uint8_t* __restrict__ keep,
-    uint64_t* __restrict__ by, unsigned long long* __restrict__ dropped) {
+    uint64_t* __restrict__ by, unsigned long long* __restrict__ dropped, MtimeRule rule) {
   const uint64_t p = (uint64_t)blockIdx.x * kResolveBlock + threadIdx.x;
   bool drop = false;
   if (p + 1 < n) {  // the last position has nothing behind it
@@ -153,7 +190,16 @@ __global__ __launch_bounds__(kResolveBlock) void ralledata_dedup_resolve_kernel(
         const Side b = side[j];
         if (b.sub != a.sub || b.klen != a.klen || !same_key(blobs + a.koff, blobs + b.koff, a.klen)) continue;
         if (by) by[i] = j;
-        drop = !(a.attrs | b.attrs);
+        if constexpr (MT) {
+          if (!(a.attrs & kHasMtime)) {
+            drop = true;
+          } else if (b.attrs & kHasMtime) {
+            const Mtime mi = rule.mt[i], mj = rule.mt[j];
+            drop = time_less(mi.sec, mi.nsec, mj.sec, mj.nsec) && time_less(mi.sec, mi.nsec, rule.sec, rule.nsec);
+          }
+        } else {
+          drop = !(a.attrs | b.attrs);
+        }
         break;
       }
       if (drop) keep[i] = 0;
@@ -171,7 +217,8 @@ __global__ __launch_bounds__(kResolveBlock) void ralledata_dedup_resolve_kernel(
 // The call's temporaries: one grow-only buffer per device, held across calls under a
 // per-device lock (the pattern of SelScratch, k2h_ralledata_check.hip) -- 56 bytes per blob
 // (two key and two index columns, the side records), the tile counts and their scan, the
-// counters, and the library's own storage.  The kernels still use the buffer after an
+// counters, and the library's own storage; the mtime rule adds 16 bytes per blob behind
+// them.  The kernels still use the buffer after an
 // asynchronous call has returned, so each call leaves an event behind and the next call's
 // stream waits for it before it writes.
 struct DedupScratch {
@@ -199,11 +246,12 @@ constexpr size_t kCounterBytes = 64 * kCounters;
 
 }  // namespace
 
-// Returns a K2H_AMD_* code (the HIP error, if any, in *herr); synchronises the stream once
-// when dropped != NULL, else not at all.  1 <= n <= 2^32 - 2.
-int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
-                           const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, hipStream_t stream,
-                           hipError_t* herr) {
+namespace {
+
+// Both entry points; pts == NULL: the attrs rule.
+int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const uint8_t* consider,
+                 uint8_t* keep, uint64_t* by, uint64_t* dropped, const k2h_amd_timespec* pts, hipStream_t stream,
+                 hipError_t* herr) {
   *herr = hipSuccess;
   const uint64_t nt = (n + kDedupBlobs - 1) / kDedupBlobs;
   hipError_t e = hipSuccess;
@@ -224,7 +272,8 @@ int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blo
   }
   const size_t c8 = align256(n * 8), c4 = align256(n * 4), cs = align256(n * sizeof(Side)), ct = align256((nt + 1) * 8);
   const size_t tmp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-  const size_t total = 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes + align256(tmp_bytes);
+  const size_t cm = pts ? align256(n * sizeof(Mtime)) : 0;  // behind everything else: the plain rule's layout stays
+  const size_t total = 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes + align256(tmp_bytes) + cm;
   DedupScratch& sc = g_dedup[dev];
   std::lock_guard<std::mutex> lk(sc.mu);
   if (!sc.done) tr(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
@@ -257,13 +306,17 @@ int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blo
   uint64_t* tile_base = (uint64_t*)(base + 2 * c8 + 2 * c4 + cs + ct);
   unsigned long long* counter = (unsigned long long*)(base + 2 * c8 + 2 * c4 + cs + 2 * ct);
   void* tmp = base + 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes;
+  Mtime* mt = (Mtime*)(base + 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes + align256(tmp_bytes));
   // entry nt of the counts is 0, so entry nt of their exclusive scan is the participants' number
   tr(hipMemsetAsync(tile_count + nt, 0, 8, stream));
   tr(hipMemsetAsync(counter, 0, kCounterBytes, stream));
   if (e == hipSuccess) {
-    ralledata_dedup_gather_kernel<<<(unsigned)nt, kDedupBlobs, 0, stream>>>((const uint8_t*)blobs, size, blob_off, n,
-                                                                          consider, keep, by, keys_out, side,
-                                                                          tile_count);
+    if (pts)
+      ralledata_dedup_gather_kernel<true><<<(unsigned)nt, kDedupBlobs, kWalkLdsBytes, stream>>>(
+          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, keys_out, side, tile_count, mt);
+    else
+      ralledata_dedup_gather_kernel<false><<<(unsigned)nt, kDedupBlobs, 0, stream>>>(
+          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, keys_out, side, tile_count, nullptr);
     tr(hipGetLastError());
   }
   if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, tile_count, tile_base, nt + 1, stream));
@@ -278,8 +331,13 @@ int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blo
   if (e == hipSuccess) {
     const uint64_t grid = (n + kResolveBlock - 1) / kResolveBlock;
     const uint64_t mask = sort_bits == 64 ? ~0ull : (1ull << sort_bits) - 1;
-    ralledata_dedup_resolve_kernel<<<(unsigned)grid, kResolveBlock, 0, stream>>>(
-        (const uint8_t*)blobs, keys_out, idx_out, n, mask, side, keep, by, counter);
+    if (pts)
+      ralledata_dedup_resolve_kernel<true><<<(unsigned)grid, kResolveBlock, 0, stream>>>(
+          (const uint8_t*)blobs, keys_out, idx_out, n, mask, side, keep, by, counter,
+          MtimeRule{mt, pts->sec, pts->nsec});
+    else
+      ralledata_dedup_resolve_kernel<false><<<(unsigned)grid, kResolveBlock, 0, stream>>>(
+          (const uint8_t*)blobs, keys_out, idx_out, n, mask, side, keep, by, counter, MtimeRule{nullptr, 0, 0});
     tr(hipGetLastError());
   }
   unsigned long long counts[8 * kCounters];
@@ -293,6 +351,23 @@ int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blo
   }
   *herr = e;
   return e != hipSuccess ? K2H_AMD_EHIP : K2H_AMD_OK;
+}
+
+}  // namespace
+
+// Returns a K2H_AMD_* code (the HIP error, if any, in *herr); synchronises the stream once
+// when dropped != NULL, else not at all.  1 <= n <= 2^32 - 2.
+int launch_ralledata_dedup(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                           const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped, hipStream_t stream,
+                           hipError_t* herr) {
+  return dedup_stages(blobs, size, blob_off, n, consider, keep, by, dropped, nullptr, stream, herr);
+}
+
+// The same with the mtime rule; pts is a host pointer, read before the call returns.
+int launch_ralledata_dedup_mtime(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                                 const uint8_t* consider, const k2h_amd_timespec* pts, uint8_t* keep, uint64_t* by,
+                                 uint64_t* dropped, hipStream_t stream, hipError_t* herr) {
+  return dedup_stages(blobs, size, blob_off, n, consider, keep, by, dropped, pts, stream, herr);
 }
 
 }  // namespace k2h

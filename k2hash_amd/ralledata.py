@@ -420,11 +420,91 @@ def import_file_to_archive(file, fmt: str = "tsv", stream=None) -> Archived:
 NO_LATER = (1 << 64) - 1  # by[i] of dedup_ralledata when no later blob has blob i's identity (-1 as int64)
 
 
-def dedup_ralledata(blobs, blob_off, consider=None, want_by: bool = False, count: bool = True, stream=None):
+def _consider_arg(consider, n, dev, torch):
+    if consider is None:
+        return None
+    if consider.dtype == torch.bool:
+        consider = consider.view(torch.uint8)
+    _check_dev(consider, "consider", torch.uint8)
+    if consider.numel() != n or consider.device != dev:
+        raise ValueError("consider needs n entries on the blobs' device")
+    return consider
+
+
+TIMES_MTIME, TIMES_EXPIRE = _native.K2H_AMD_TIMES_MTIME, _native.K2H_AMD_TIMES_EXPIRE
+TIMES_CUT, TIMES_ATTRS = _native.K2H_AMD_TIMES_CUT, _native.K2H_AMD_TIMES_ATTRS
+
+
+class TimeWindow:
+    """The time arguments of K2HShm::GetElementListToBinary (lib/k2hshmdirect.cc:103): start and
+    end bound the mtime (pstartts, pendts), now switches the expiry check on (is_expire_check,
+    with the clock's value passed in).  Each is a (sec, nsec) tuple or None."""
+
+    def __init__(self, start=None, end=None, now=None):
+        self.start, self.end, self.now = start, end, now
+
+    def ctypes(self) -> "_native.TimeWindowStruct":
+        flags = 0
+        ts = []
+        for bit, t in ((_native.K2H_AMD_WIN_START, self.start), (_native.K2H_AMD_WIN_END, self.end),
+                       (_native.K2H_AMD_WIN_EXPIRE, self.now)):
+            flags |= bit if t is not None else 0
+            ts.append(_native.Timespec(*(int(x) for x in t)) if t is not None else _native.Timespec(0, 0))
+        return _native.TimeWindowStruct(flags, 0, *ts)
+
+
+class Times(NamedTuple):
+    flags: object   # uint8 tensor, n: TIMES_MTIME | TIMES_EXPIRE | TIMES_CUT | TIMES_ATTRS
+    mtime: object   # int64 tensor, (n, 2): sec, nsec; 0, 0 when absent
+    expire: object  # int64 tensor, (n, 2)
+    keep: object    # uint8 tensor, n
+
+
+def blob_times(blobs, blob_off, consider=None, window: Optional[TimeWindow] = None, route=None,
+               stream=None) -> Times:
+    """The builtin mtime and expire inside every blob's serialized attrs, and the time selection
+    of GetElementListToBinary (k2h_amd_ralledata_times).  consider: the blobs that take part
+    (None: all); a blob that does not, or whose span or header is bad, gets flags 0, zero times
+    and keep 0.  keep[i] of a participant: 0 when window.now is given and the blob is expired
+    then; else, for a blob with an mtime, 0 when it is before window.start (only for blobs whose
+    route byte has ROUTE_OLD; route None: for all) or after window.end; else 1.  Without a
+    window keep is the participants.  route: the uint8 tensor of check_ralledata (needs a
+    window).  Asynchronous on the stream."""
+    torch = _torch()
+    n = _check_stream(blobs, blob_off, torch)
+    dev = blobs.device
+    consider = _consider_arg(consider, n, dev, torch)
+    if route is not None:
+        if window is None:
+            raise ValueError("route needs a window")
+        _check_dev(route, "route", torch.uint8)
+        if route.numel() != n or route.device != dev:
+            raise ValueError("route needs n entries on the blobs' device")
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    mtime = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    expire = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    win = window.ctypes() if window is not None else None
+    opt = lambda t: ctypes.c_void_p(t.data_ptr() or 1) if t is not None and n else None  # noqa: E731
+    full = lambda t: ctypes.c_void_p(t.data_ptr() or 1)  # noqa: E731
+    rc = _native.batch_lib().k2h_amd_ralledata_times(
+        full(blobs), blobs.numel(), _dev_ptr(blob_off), n, opt(consider),
+        ctypes.byref(win) if win is not None else None, opt(route), full(flags), full(mtime), full(expire),
+        full(keep), _stream_handle(stream))
+    _native.check(rc)
+    return Times(flags, mtime, expire, keep)
+
+
+def dedup_ralledata(blobs, blob_off, consider=None, want_by: bool = False, count: bool = True, stream=None,
+                    pts=None):
     """The blobs of a stream worth feeding to k2h_set_element_by_binary
     (k2h_amd_ralledata_dedup).  Two blobs have the same identity when their stored hash,
     stored subhash, key length and key bytes are equal; blob i is superseded -- keep[i] = 0 --
     when the nearest later blob of its identity exists and neither of the two carries attrs.
+    pts: the (sec, nsec) the whole stream will be fed with; with it the mtime rule applies
+    instead (k2h_amd_ralledata_dedup_mtime): blob i is superseded by the nearest later blob j of
+    its identity when i has no mtime, or both have one and m_i < m_j and m_i < pts -- so blobs
+    with attrs are dropped too, and every blob the plain rule drops.
     consider: uint8 or bool tensor of n, the blobs that take part (None: all); a blob that
     does not, or whose span or header is bad, gets keep[i] = 0 and supersedes nothing.
     Returns (keep, by, dropped): keep a uint8 tensor of n; by (want_by) an int64 tensor of n,
@@ -443,26 +523,37 @@ def dedup_ralledata(blobs, blob_off, consider=None, want_by: bool = False, count
     keep = torch.empty(n, dtype=torch.uint8, device=dev)
     by = torch.empty(n, dtype=torch.int64, device=dev) if want_by else None
     dropped = ctypes.c_uint64(0)
-    rc = _native.batch_lib().k2h_amd_ralledata_dedup(
-        ctypes.c_void_p(blobs.data_ptr() or 1), blobs.numel(), _dev_ptr(blob_off), n,
-        _dev_ptr(consider) if consider is not None and n else None, ctypes.c_void_p(keep.data_ptr() or 1),
-        _dev_ptr(by) if want_by and n else None, ctypes.byref(dropped) if count else None, _stream_handle(stream))
+    args = (ctypes.c_void_p(blobs.data_ptr() or 1), blobs.numel(), _dev_ptr(blob_off), n,
+            _dev_ptr(consider) if consider is not None and n else None, ctypes.c_void_p(keep.data_ptr() or 1),
+            _dev_ptr(by) if want_by and n else None, ctypes.byref(dropped) if count else None)
+    if pts is None:
+        rc = _native.batch_lib().k2h_amd_ralledata_dedup(*args, _stream_handle(stream))
+    else:
+        ts = _native.Timespec(int(pts[0]), int(pts[1]))
+        rc = _native.batch_lib().k2h_amd_ralledata_dedup_mtime(*args, ctypes.byref(ts), _stream_handle(stream))
     _native.check(rc)
     return keep, by, int(dropped.value) if count else None
 
 
 def route_ralledata(blobs, blob_off, hash_range: HashRange, std_fnv: bool = False, stream=None,
-                    dedup: bool = False):
+                    dedup: bool = False, window: Optional[TimeWindow] = None, pts=None):
     """What a receiver that owns `hash_range` does with a stream: check it, then keep the
     blobs that are OK and whose hash is in the target range (status == 0 and route & 1).
-    dedup: of those, also leave out the ones a later one supersedes (dedup_ralledata).
+    window: of those, only the ones GetElementListToBinary's time selection lets through
+    (blob_times with the check's route, so the start bound applies to the old range only).
+    dedup: of those, also leave out the ones a later one supersedes (dedup_ralledata; with pts
+    by the mtime rule).
     Returns (Selected, CheckResult); the kept blobs feed k2h_set_element_by_binary."""
     torch = _torch()
     res = check_ralledata(blobs, blob_off, hash_range, std_fnv=std_fnv, stream=stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         keep = ((res.status == OK) & ((res.route & ROUTE_TARGET) != 0)).to(torch.uint8)
+    if window is not None:
+        timed = blob_times(blobs, blob_off, consider=keep, window=window, route=res.route, stream=stream).keep
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            keep = keep & timed
     if dedup:
-        live, _by, _dropped = dedup_ralledata(blobs, blob_off, consider=keep, count=False, stream=stream)
+        live, _by, _dropped = dedup_ralledata(blobs, blob_off, consider=keep, count=False, stream=stream, pts=pts)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
             keep = keep & live
     return select_ralledata(blobs, blob_off, keep, stream=stream), res
