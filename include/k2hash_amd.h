@@ -693,6 +693,85 @@ int k2h_amd_archive_scan_prehash_device(const void* file, uint64_t size, k2h_amd
                                         uint64_t* count, uint64_t* h1, uint64_t* h2, uint64_t* new_h1,
                                         uint64_t* new_h2, uint32_t flags, void* stream);
 
+/* 5b. A transaction archive folded to the records that still matter: log compaction by the
+ * rule of K2HArchive::Load, for a log already in device memory.  K2HTransaction writes such a
+ * log from a live table: Set emits SET_ALL (lib/k2hshm.cc:2314), Remove DEL_KEY (:2711),
+ * ReplaceValue / ReplaceSubkeys / AddSubkey / ReplaceAttrs emit REPLACE_VAL / REPLACE_SKEY /
+ * REPLACE_ATTRS (:3099-3123), direct access OW_VAL, Rename RENAME.  The blob route
+ * (k2h_amd_archive_ralledata + k2h_amd_ralledata_dedup) is for Save outputs only: it turns
+ * nothing but SET_ALL into blobs, so a key set and then removed comes back, and its whole-blob
+ * rule is SetElementByBinArray's, not Load's.  Device pointers only (file, recs, h1, keep, by);
+ * dropped is a host pointer.
+ *
+ * The rule.  Per key a table element is (exists, V, S, A).  Load's switch
+ * (lib/k2harchive.cc:328-363) goes through K2HShm::ReplaceAll (lib/k2hshm.cc:2948-2950),
+ * K2HShm::Replace (:2973-3036), ReplacePage (:3168-3225) and Remove(key, false) (:2544-2560,
+ * RemoveEx :2789-2820).  Each record type writes a set of fields W:
+ *   SET_ALL         V always (an empty value clears it), S if skey_length > 0, A if
+ *                   attr_length > 0
+ *   REPLACE_VAL / REPLACE_SKEY / REPLACE_ATTRS
+ *                   {V} / {S} / {A} (empty data clears the field; a missing key is created with
+ *                   only that field)
+ *   DEL_KEY         {V, S, A} (the element is freed; removing an absent key succeeds, :2817-2819)
+ *   OW_VAL, RENAME  barriers: always kept, nothing folds across them
+ *
+ * Participants.  Record i takes part when status == 0, type is in 0..6, key_len >= 1 and the
+ * key range is inside [0, size) (off <= size && len <= size - off, checked again on the device:
+ * recs are the caller's).  Every other record gets keep 0: these are the records Load with
+ * isErrSkip skips.
+ * Identity.  Two participants address the same element when key_len and the key bytes are equal.
+ * Segment.  seg(i) = the number of participants of type RENAME before i in record order.
+ * Rename touches two keys and possibly more, so it is a barrier for every key.
+ * Chain.  The chain of i is the later participants of i's identity in record order, cut before
+ * the first one that is OW_VAL or RENAME or whose seg differs from seg(i).
+ * Drop.  A participant i of type SET_ALL, REPLACE_* or DEL_KEY is dropped exactly when W(i) is a
+ * subset of the union of W(j) over its chain.  A dropped i is not the last writer of any of its
+ * fields and, W(i) being non-empty, not the last record of its key: at the chain record where
+ * the cover completes the element is the same with and without i, and no barrier lies between.
+ * So the kept records, replayed in order, leave the table that the whole log leaves, from any
+ * prior table.  [SET_ALL(k, v1, skeys = S), SET_ALL(k, v2, skeys = "")] keeps both records
+ * (Load gives (v2, S)); [SET_ALL, DEL_KEY] keeps only the delete.
+ *
+ * Preconditions.  The table has no builtin attributes and no history switched on (otherwise
+ * Set on a missing key adds attrs of its own and Remove renames for history).  The subkeys and
+ * attrs segments are ones K2HSubKeys / K2HAttrs::Serialize accept, as the library's writer
+ * produces them.  Parity with Load is a restatement: libk2hash itself is not built by this
+ * project's tests (it needs libfullock).  Merging a key's surviving records into one SET_ALL
+ * is not done.
+ *
+ *   h1       (n entries, may be NULL) k2h_hash of each key, as k2h_amd_archive_prehash gives it.
+ *            Only a grouping key: identity is always decided on key length and key bytes, and
+ *            values that are equal for different keys only cost time.  Records of equal keys
+ *            must carry equal values (any function of the key bytes will do, all zeros included);
+ *            records of one key under different values are not brought together.  NULL: the
+ *            call computes it (default seed) by the prehash path.
+ *   keep[i]  (n entries, required) 0 for a non-participant and for a dropped participant, else 1
+ *   by[i]    (n entries, may be NULL) the nearest later participant of i's identity, barrier or
+ *            not, in any seg; ~0 when there is none, and for a non-participant
+ *   *dropped (host, may be NULL) the number of dropped participants
+ *
+ * n == 0: K2H_AMD_OK, *dropped = 0, no device work.  K2H_AMD_EINVAL, judged on the host before
+ * any device is touched, each with its own message: keep, file or recs NULL with n > 0;
+ * n > 2^32 - 2 (indices are sorted as 32-bit values).
+ *
+ * Stages (k2hash_amd/csrc/k2h_archive_fold.hip): a gather pass over the records, one library
+ * radix sort of (h1, index) pairs on the hash's low bits, a link pass that walks to the nearest
+ * later record of the same key (it reads only keys whose hash occurs more than once), and a
+ * cover by pointer doubling over the chains, so that a key with a million records costs about
+ * 20 rounds over 8 bytes per record and not a million dependent loads in one lane.  The host
+ * reads one word after the link pass and after every cover round to learn whether a record is
+ * still undecided: the call synchronises `stream` once, plus once per round -- about
+ * log2 of the longest run of one key's records that ends in a record left uncovered: six on the
+ * measured 8 Mi-record log with a quarter rewrites, 20 for a key with a million records, at most
+ * 32 -- plus once when dropped != NULL.  It is never fully asynchronous.  r DISTINCT keys
+ * under one h1 cost O(r^2) key compares (wrong h1 values only).
+ *
+ * No byte outside [0, size) is read except within the aligned 16 bytes that hold a valid byte;
+ * nothing of a record is read but its key, and nothing of a non-participant.  Temporary device
+ * memory: about 72 bytes per record plus the sort's own, kept per device between calls. */
+int k2h_amd_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
+                         const uint64_t* h1, uint8_t* keep, uint64_t* by, uint64_t* dropped, void* stream);
+
 /* k2himport inputs (tests/k2himport.cc:74-117): k2h_amd_import_scan splits a TSV
  * (key TAB value NEWLINE) or mdbm_export file (five header lines ending "HEADER=END",
  * then key line / value line) into records exactly as the tool's std::getline loops

@@ -114,6 +114,7 @@ SIGNATURES = {
     "k2h_amd_archive_prehash": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_scan_prehash_device": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p,
                                                            ctypes.c_uint32, _p]),
+    "k2h_amd_archive_fold": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _p]),
     "k2h_amd_import_scan": (ctypes.c_int, [_p, _u64, ctypes.c_int, _p, _u64, _p]),
     "k2h_amd_import_prehash_host": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, ctypes.c_uint32, ctypes.c_int]),
     "k2h_amd_import_scan_device": (ctypes.c_int, [_p, _u64, ctypes.c_int, _p, _u64, _p, _p]),

@@ -9,6 +9,7 @@ hashes every key of the file in one GPU batch.
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -143,6 +144,78 @@ def scan_prehash_device(file, rename: bool = False, std_fnv: bool = False, strea
     _native.check(rc)
     n = cnt.value
     return (recs[:n],) + tuple(x[:n] for x in out)
+
+
+NO_LATER = (1 << 64) - 1  # by[i] without a later record of the same key (-1 in the int64 tensor)
+
+
+class Folded(NamedTuple):
+    keep: object              # uint8 tensor, n: 1 for the records that still matter
+    by: Optional[object]      # int64 tensor, n (want_by): the nearest later participant of the same key, or -1
+    dropped: Optional[int]    # the number of dropped participants (count)
+    recs: object              # the (n, 13) int64 records the fold ran over
+
+
+def fold_device(file, recs=None, h1=None, want_by: bool = False, count: bool = True, stream=None) -> Folded:
+    """The records of a transaction archive in device memory that still matter under
+    K2HArchive::Load's rule (k2h_amd_archive_fold): record i is dropped -- keep[i] = 0 -- when
+    the fields it writes (SET_ALL: the value, and subkeys / attrs when its own are non-empty;
+    REPLACE_*: the one field; DEL_KEY: all three) are all written again by later records of its
+    key, before any OW_VAL or RENAME of that key and any RENAME of the log.  Replaying the kept
+    records in order leaves the table the whole log leaves.  Records Load skips get keep 0.
+    recs: the records of scan_device (None: scan_prehash_device runs here and its hashes are
+    passed on); h1: k2h_hash of each key as prehash_device gives it (only a grouping key; None
+    with recs given: computed inside the call).  The call synchronises the stream once after
+    its link stage, once per cover round (about log2 of the longest run of one key's records)
+    and once more for the count."""
+    torch = _torch()
+    _check_dev(file, "file", torch.uint8)
+    if recs is None:
+        recs, h1 = scan_prehash_device(file, stream=stream)[:2]
+    _check_recs(torch, recs)
+    n = recs.shape[0]
+    dev = file.device
+    if recs.device != dev:
+        raise ValueError("file and recs are on different devices")
+    if h1 is not None:
+        _check_dev(h1, "h1", torch.int64)
+        if h1.numel() != n or h1.device != dev:
+            raise ValueError("h1 needs n entries on the file's device")
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    by = torch.empty(n, dtype=torch.int64, device=dev) if want_by else None
+    dropped = ctypes.c_uint64(0)
+    _native.check(_native.batch_lib().k2h_amd_archive_fold(
+        ctypes.c_void_p(file.data_ptr() or 1), file.numel(), ctypes.c_void_p(recs.data_ptr() or 1), n,
+        _dev_ptr(h1) if h1 is not None and n else None, ctypes.c_void_p(keep.data_ptr() or 1),
+        _dev_ptr(by) if want_by and n else None, ctypes.byref(dropped) if count else None, _stream_handle(stream)))
+    return Folded(keep, by, int(dropped.value) if count else None, recs)
+
+
+class Compacted(NamedTuple):
+    bytes: object      # uint8 tensor: the compacted archive, the kept records byte for byte, in order
+    index: object      # int64 tensor, kept: the kept records' indices in the input
+    kept: int
+    kept_bytes: int
+    records: int       # records of the input
+
+
+def compact_device(file, stream=None) -> Compacted:
+    """A transaction archive in device memory compacted by Load's rule: scan_prehash_device,
+    fold_device, then k2h_amd_ralledata_select as the byte copier over the records' own spans
+    (record i = file[offset[i], offset[i + 1]), the last one 104 + its five lengths long).  The
+    output is a k2hash archive that K2HArchive::Load replays into the table the input gives."""
+    torch = _torch()
+    from .ralledata import select_ralledata  # (ralledata imports this module)
+    folded = fold_device(file, count=False, stream=stream)
+    recs = folded.recs
+    n = recs.shape[0]
+    if n == 0:
+        return Compacted(file[:0].clone(), torch.empty(0, dtype=torch.int64, device=file.device), 0, 0, 0)
+    rec_off = torch.empty(n + 1, dtype=torch.int64, device=file.device)
+    rec_off[:n] = recs[:, 1]
+    rec_off[n] = recs[n - 1, 1] + _native.K2H_AMD_SCOM_HEADER + recs[n - 1, 3:12:2].sum()
+    sel = select_ralledata(file, rec_off, folded.keep, stream=stream)
+    return Compacted(sel.blobs, sel.index, sel.kept, sel.kept_bytes, n)
 
 
 def hash_ranges(base, starts, lens, second: bool = False, cstr: bool = False, std_fnv: bool = False, stream=None):

@@ -679,6 +679,25 @@ __attribute__((visibility("default"))) int k2h_amd_archive_scan_prehash_device(
                           : fail(rc, "archive_scan_prehash_device: more records than cap, or too many candidates");
 }
 
+// Section 5b: a transaction archive folded by Load's rule.  Judged on the host before any
+// device is touched.
+__attribute__((visibility("default"))) int k2h_amd_archive_fold(const void* file, uint64_t size,
+                                                                const k2h_amd_archive_rec* recs, uint64_t n,
+                                                                const uint64_t* h1, uint8_t* keep, uint64_t* by,
+                                                                uint64_t* dropped, void* stream) {
+  if (dropped) *dropped = 0;
+  if (n == 0) return K2H_AMD_OK;
+  if (!keep) return fail(K2H_AMD_EINVAL, "archive_fold: NULL keep");
+  if (!file) return fail(K2H_AMD_EINVAL, "archive_fold: NULL file");
+  if (!recs) return fail(K2H_AMD_EINVAL, "archive_fold: NULL recs");
+  if (n > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL, "archive_fold: more than 2^32 - 2 records (indices are sorted as 32-bit values)");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_archive_fold(file, size, recs, n, h1, seed_for(0), keep, by, dropped, (hipStream_t)stream, &e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_archive_fold", e);
+}
+
 // ---------------------------------------------------------------------------
 // RALLEDATA producer (include/k2hash_amd.h section 4)
 // ---------------------------------------------------------------------------

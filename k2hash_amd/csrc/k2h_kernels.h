@@ -199,6 +199,14 @@ int launch_archive_scan(const void* file, uint64_t size, k2h_amd_archive_rec* re
 hipError_t launch_archive_prehash(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
                                   uint64_t seed, const ArchiveHashOut& hash, hipStream_t stream);
 
+// Log compaction by Load's rule (k2h_archive_fold.hip).  Returns a K2H_AMD_* code (the HIP
+// error in *herr).  h1 == NULL: the keys are hashed with `seed` by launch_archive_prehash.
+// Synchronises the stream once after the link stage, once per cover round, and once more when
+// dropped != NULL.  1 <= n <= 2^32 - 2.
+int launch_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
+                        const uint64_t* h1, uint64_t seed, uint8_t* keep, uint64_t* by, uint64_t* dropped,
+                        hipStream_t stream, hipError_t* herr);
+
 // S_p = seed * P^-p (p = 0..15): start states for end-aligned chunking (k2h_csr.hip).
 struct SpadTable {
   uint64_t v[16];
