@@ -484,6 +484,97 @@ int k2h_amd_ralledata_dedup_mtime(const void* blobs, uint64_t size, const uint64
                                   const uint8_t* consider, uint8_t* keep, uint64_t* by, uint64_t* dropped,
                                   const k2h_amd_timespec* pts, void* stream);
 
+/* 4b'''''. Two streams joined by identity: what an incoming stream changes.  The calls above
+ * judge a stream against itself; a receiver's question compares two.  A is the incoming stream
+ * (the output of k2h_get_elements_by_hash on a peer), B the held stream: a dump of what the
+ * local table holds for the identities in question.  For every blob of A that the table
+ * already holds, K2HShm::SetElementByBinArray (lib/k2hshmdirect.cc:343-478) takes the CKINDEX
+ * write lock, finds the element and parses its attrs, and then returns early (:402-405,
+ * :416-419, :421-427) or frees an element only to allocate the same bytes again.  This call
+ * says which blobs of A are worth that.  Device pointers except `times` and `counts`.
+ *
+ * Participants, in both streams, by the rule of _dedup: consider is NULL or consider[i] != 0,
+ * the span is good and the header is not EMPTY, NO_KEY or BAD_RANGE.  Identity is that of
+ * section 4b': stored hash, stored subhash, key_length, key bytes; the hash fields are trusted,
+ * not recomputed (compose with _check through the consider arrays).
+ *
+ *   match[i] (na entries, may be NULL) the index in B of the LAST participant of B with i's
+ *            identity; ~0 when there is none, and for a non-participant of A.  A dump holds one
+ *            blob per identity; of a B that holds several the last one is taken.
+ *   rel[i]   (na entries, required) 0 for a non-participant; else K2H_AMD_DIFF_PART, and
+ *            _DATA  when any of i's value, subkeys and attrs lengths is non-zero (:438);
+ *            _FOUND when match[i] != ~0; with it one of _VAL, _SKEY, _ATTRS per segment that
+ *                   differs from the matched blob's.  Two segments are equal when their lengths
+ *                   are equal and, where the length is non-zero, their bytes are; the pos of a
+ *                   length-0 segment is ignored, and unequal lengths set the bit without a
+ *                   payload byte being read;
+ *            _REPEAT when another participant of A stores i's 64-bit hash: an over-approximation
+ *                   of "another blob of A has i's identity" that needs no key read;
+ *            _APPLY only when `times` is given.  Not FOUND: set (the path falls through at
+ *                   :377-378).  FOUND: :380-431 with the matched blob's attrs as the existing
+ *                   element's, in this order: set if the matched blob has attrs_length == 0 (no
+ *                   attrs page, GetAttrs NULL); set if it is expired at times->now; set if it
+ *                   has no mtime; clear if pts <= m_b (:402); set if i has an mtime and
+ *                   m_b < m_i; clear otherwise (:416, :426).  Times are read and compared as in
+ *                   section 4b''''.
+ *   seen[j]  (nb entries, may be NULL) 1 when some participant of A has match == j, else 0; all
+ *            nb entries are written.  The blobs of B with seen 0 are the held elements A does
+ *            not mention.  Removing them is not done here or anywhere: seen only reports them.
+ *   counts   (host, 4 entries, may be NULL) participants of A, FOUND, FOUND with no differ bit,
+ *            APPLY.  counts != NULL: `stream` is synchronised once; else the call is
+ *            asynchronous.
+ *
+ * What the bits are for.  Let change(i) = FOUND ? (VAL | SKEY | ATTRS) != 0 : DATA, and
+ * feed(i) = PART && (REPEAT || (APPLY && change(i))).  Feeding only the blobs with feed leaves
+ * the table that feeding all of A leaves, provided B holds the table's element for every
+ * identity of A that the table has, and no other; one pts is used for the whole feed; now is
+ * the clock at feed time; and an expired element stays expired.  A blob without APPLY returns
+ * early; one with APPLY and no change frees an element (or finds none) and stores the same
+ * bytes (or none).  A REPEAT blob is always fed: its verdict against B goes stale as soon as an
+ * earlier blob of its key is applied -- an applied blob that is itself expired lets any later
+ * blob overwrite it.  tests/test_ralledata_diff.py replays this on the CPU against a
+ * transliteration of SetElementByBinArray; libk2hash itself is not built by this project, so
+ * parity with it is a restatement, as in the sections above.
+ *
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ * rel NULL with na > 0; a stream's blobs or offsets NULL with its n > 0; na + nb > 2^32 - 2
+ * (indices of both streams are sorted as 32-bit values of one space).  na == 0: K2H_AMD_OK,
+ * counts zeroed, seen (if given) zeroed by one memset on `stream`.  nb == 0 is an ordinary call
+ * in which nothing is found.
+ *
+ * No byte outside [0, size) of either stream is read except within the aligned 16 bytes that
+ * hold a valid byte; nothing of a blob whose span is bad or whose consider byte is 0, nothing
+ * of a non-participant beyond its header, and no payload byte of a pair whose segment lengths
+ * differ.  All absolute offsets are 64-bit.
+ *
+ * Cost: a gather pass over both streams' headers (with times also over the attrs of the blobs
+ * that have some), one library radix sort of na + nb (stored hash, index) pairs on the hash's
+ * low bits, one max-scan, a resolve pass that reads the keys of the blobs whose stored hash
+ * occurs in both streams, and a compare pass that reads the equal-length segments of every
+ * matched pair from both streams.  r copies of one key in A, matched or not, cost O(1) steps
+ * each; r DISTINCT identities that agree in all sorted bits, in A or in B, cost O(r) steps per
+ * blob of A among them -- the crafted-stream case of section 4b'.  Temporary device memory, kept
+ * per device between calls: 57 bytes per blob of na + nb (the 56 of _dedup and a participant
+ * byte; the scan column and the compare's work items reuse the sort's input columns) plus the
+ * sort's own, and 16 bytes per blob more with times. */
+#define K2H_AMD_DIFF_PART 0x01u   /* A blob i takes part */
+#define K2H_AMD_DIFF_FOUND 0x02u  /* a held blob of i's identity exists */
+#define K2H_AMD_DIFF_VAL 0x04u    /* FOUND, and the value segments differ */
+#define K2H_AMD_DIFF_SKEY 0x08u   /* FOUND, and the subkeys segments differ */
+#define K2H_AMD_DIFF_ATTRS 0x10u  /* FOUND, and the attrs segments differ */
+#define K2H_AMD_DIFF_DATA 0x20u   /* i has a value, subkeys or attrs (lib/k2hshmdirect.cc:438) */
+#define K2H_AMD_DIFF_REPEAT 0x40u /* another participant of A stores i's hash */
+#define K2H_AMD_DIFF_APPLY 0x80u  /* with times: SetElementByBinArray would not return early */
+
+typedef struct k2h_amd_diff_times {
+  k2h_amd_timespec pts, now;
+} k2h_amd_diff_times;
+
+int k2h_amd_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* a_off, uint64_t na,
+                           const uint8_t* a_consider, const void* b_blobs, uint64_t b_size, const uint64_t* b_off,
+                           uint64_t nb, const uint8_t* b_consider, const k2h_amd_diff_times* times, uint8_t* rel,
+                           uint64_t* match, uint8_t* seen, uint64_t* counts, void* stream);
+
 /* 4c. Blobs straight from scanned records: the middle of a bulk load whose file is already
  * in device memory.  The device scans of section 5 (k2h_amd_import_scan_device,
  * k2h_amd_archive_scan_device and their _scan_prehash_device forms) report every record as

@@ -11,7 +11,8 @@ and (2) a batch C ABI backed by hand-written gfx950 HIP kernels (section 2).
   ralledata  RALLEDATA direct-set blobs: built on the GPU (from CSR streams, or straight
              from the records of a scanned import file or archive), and blob streams
              checked, routed by hash range, compacted and split into owner or lock
-             partitions there, and written out as a k2hash archive
+             partitions there, written out as a k2hash archive, and two streams joined by
+             identity (what an incoming stream changes in a held one)
   archive    k2hash archives scanned and prehashed on the GPU, and transaction logs folded to
              the records that still matter under Load's rule (fold_device, compact_device)
   shard      multi-GPU partitioning and the RCCL gather of hashes
@@ -21,8 +22,8 @@ from .hashfunc import (K2H_2ND_HASH_FUNC, K2H_HASH_FUNC, K2H_HASH_VER_FUNC, K2Ha
 from .batch import (bucket_index, hash_csr, hash_csr_host, hash_csr_index, hash_fixed, hash_fixed_host,
                     hash_fixed_index, synth_bytes, synth_offsets, unpack_kindex, version)
 from .archive import compact_device, fold_device
-from .ralledata import (HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
-                        dedup_ralledata, import_file_to_archive, import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
+from .ralledata import (Diff, HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
+                        dedup_ralledata, diff_ralledata, import_file_to_archive, import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
                         ralledata_to_archive, route_ralledata, select_ralledata)
 
 __all__ = [
@@ -32,5 +33,5 @@ __all__ = [
     "hash_csr_index", "unpack_kindex", "check_ralledata", "select_ralledata", "route_ralledata", "HashRange",
     "make_hash_range", "import_to_ralledata", "archive_to_ralledata", "import_file_to_ralledata",
     "dedup_ralledata", "partition_ralledata", "ralledata_to_archive", "import_file_to_archive",
-    "blob_times", "TimeWindow", "Times", "fold_device", "compact_device",
+    "blob_times", "TimeWindow", "Times", "fold_device", "compact_device", "diff_ralledata", "Diff",
 ]

@@ -75,7 +75,16 @@ class TimeWindowStruct(ctypes.Structure):
                 ("now", Timespec)]
 
 
+class DiffTimes(ctypes.Structure):
+    """k2h_amd_diff_times (include/k2hash_amd.h section 4b'''''): the pts the feed will use and the clock."""
+    _fields_ = [("pts", Timespec), ("now", Timespec)]
+
+
+K2H_AMD_DIFF_PART, K2H_AMD_DIFF_FOUND, K2H_AMD_DIFF_VAL, K2H_AMD_DIFF_SKEY = 0x01, 0x02, 0x04, 0x08
+K2H_AMD_DIFF_ATTRS, K2H_AMD_DIFF_DATA, K2H_AMD_DIFF_REPEAT, K2H_AMD_DIFF_APPLY = 0x10, 0x20, 0x40, 0x80
+
 _twp = ctypes.POINTER(TimeWindowStruct)
+_dtp = ctypes.POINTER(DiffTimes)
 _tsp = ctypes.POINTER(Timespec)
 
 # name -> (restype, argtypes); mirrors include/k2hash_amd.h
@@ -102,6 +111,8 @@ SIGNATURES = {
     "k2h_amd_ralledata_dedup": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _p]),
     "k2h_amd_ralledata_times": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _twp, _p, _p, _p, _p, _p, _p]),
     "k2h_amd_ralledata_dedup_mtime": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _tsp, _p]),
+    "k2h_amd_ralledata_diff": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _p, _dtp, _p, _p, _p, _u64p,
+                                              _p]),
     "k2h_amd_ralledata_partition": (ctypes.c_int, [_p, _u64, _p, _u64, _prp, _p, _p, _p, _u64, _p, _p, _p, _u64p,
                                                    _u64p, _p]),
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),

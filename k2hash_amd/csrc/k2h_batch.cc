@@ -902,6 +902,32 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_dedup_mtime(
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_dedup_mtime", e);
 }
 
+// Section 4b''''': two streams joined by identity.  Judged on the host like the ones above.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_diff(
+    const void* a_blobs, uint64_t a_size, const uint64_t* a_off, uint64_t na, const uint8_t* a_consider,
+    const void* b_blobs, uint64_t b_size, const uint64_t* b_off, uint64_t nb, const uint8_t* b_consider,
+    const k2h_amd_diff_times* times, uint8_t* rel, uint64_t* match, uint8_t* seen, uint64_t* counts, void* stream) {
+  if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  if (na && !rel) return fail(K2H_AMD_EINVAL, "ralledata_diff: NULL rel");
+  if (na && !a_blobs) return fail(K2H_AMD_EINVAL, "ralledata_diff: NULL a_blobs");
+  if (na && !a_off) return fail(K2H_AMD_EINVAL, "ralledata_diff: NULL a_off");
+  if (nb && !b_blobs) return fail(K2H_AMD_EINVAL, "ralledata_diff: NULL b_blobs");
+  if (nb && !b_off) return fail(K2H_AMD_EINVAL, "ralledata_diff: NULL b_off");
+  if (na > 0xFFFFFFFEull || nb > 0xFFFFFFFEull || na + nb > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL,
+                "ralledata_diff: more than 2^32 - 2 blobs in the two streams (indices are sorted as 32-bit values)");
+  if (na == 0 && !(seen && nb)) return K2H_AMD_OK;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  if (na == 0) {  // nothing arrives: no held blob is mentioned
+    e = hipMemsetAsync(seen, 0, nb, (hipStream_t)stream);
+    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_diff: hipMemsetAsync", e);
+  }
+  int rc = k2h::launch_ralledata_diff(a_blobs, a_size, a_off, na, a_consider, b_blobs, b_size, b_off, nb, b_consider,
+                                      times, rel, match, seen, counts, (hipStream_t)stream, &e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_diff", e);
+}
+
 // Section 4b'': the stream split into parts.  Judged on the host like the three above.
 __attribute__((visibility("default"))) int k2h_amd_ralledata_partition(
     const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const k2h_amd_part_rule* rule,

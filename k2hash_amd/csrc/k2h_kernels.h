@@ -135,6 +135,14 @@ int launch_ralledata_dedup_mtime(const void* blobs, uint64_t size, const uint64_
                                  const uint8_t* consider, const k2h_amd_timespec* pts, uint8_t* keep, uint64_t* by,
                                  uint64_t* dropped, hipStream_t stream, hipError_t* herr);
 
+// Two streams joined by identity (k2h_ralledata_diff.hip): A the incoming stream, B the held one.
+// Returns a K2H_AMD_* code (the HIP error in *herr); synchronises the stream once when
+// counts != NULL.  na >= 1, na + nb <= 2^32 - 2; times is a host pointer, read before the return.
+int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* a_off, uint64_t na,
+                          const uint8_t* a_consider, const void* b_blobs, uint64_t b_size, const uint64_t* b_off,
+                          uint64_t nb, const uint8_t* b_consider, const k2h_amd_diff_times* times, uint8_t* rel,
+                          uint64_t* match, uint8_t* seen, uint64_t* counts, hipStream_t stream, hipError_t* herr);
+
 // The mtime and expire of every blob's attrs and the time-window selection
 // (k2h_ralledata_times.hip).  Asynchronous on the stream; n >= 1, window may be NULL.
 hipError_t launch_ralledata_times(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,

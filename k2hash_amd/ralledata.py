@@ -535,6 +535,76 @@ def dedup_ralledata(blobs, blob_off, consider=None, want_by: bool = False, count
     return keep, by, int(dropped.value) if count else None
 
 
+DIFF_PART, DIFF_FOUND, DIFF_VAL, DIFF_SKEY = (_native.K2H_AMD_DIFF_PART, _native.K2H_AMD_DIFF_FOUND,
+                                              _native.K2H_AMD_DIFF_VAL, _native.K2H_AMD_DIFF_SKEY)
+DIFF_ATTRS, DIFF_DATA, DIFF_REPEAT, DIFF_APPLY = (_native.K2H_AMD_DIFF_ATTRS, _native.K2H_AMD_DIFF_DATA,
+                                                  _native.K2H_AMD_DIFF_REPEAT, _native.K2H_AMD_DIFF_APPLY)
+NO_MATCH = (1 << 64) - 1  # match[i] of diff_ralledata when B holds no blob of i's identity (-1 as int64)
+
+
+class Diff(NamedTuple):
+    rel: object           # uint8 tensor, na: DIFF_* bits
+    match: object         # int64 tensor, na, or None: the matched blob of B, -1 without one
+    seen: object          # uint8 tensor, nb, or None: 1 for a blob of B some blob of A matched
+    participants: object  # the four counts (None with count=False): participants of A,
+    found: object         # ... those with a held blob of their identity,
+    same: object          # ... those of them whose three segments all equal the held blob's,
+    apply: object         # ... and the blobs SetElementByBinArray would go on to write (0 without pts)
+    feed: object          # uint8 tensor, na, or None without pts: the blobs worth feeding
+
+
+def diff_ralledata(a_blobs, a_off, b_blobs, b_off, a_consider=None, b_consider=None, pts=None, now=None,
+                   want_match: bool = False, want_seen: bool = False, count: bool = True, stream=None) -> Diff:
+    """What the incoming stream A changes in a table whose elements the held stream B dumps
+    (k2h_amd_ralledata_diff).  Every participant of A is joined with the last participant of B
+    of its identity -- stored hash, stored subhash, key length, key bytes -- and the value,
+    subkeys and attrs segments of the pair are compared: rel[i] carries DIFF_PART, DIFF_DATA,
+    DIFF_FOUND, one of DIFF_VAL / DIFF_SKEY / DIFF_ATTRS per segment that differs, and
+    DIFF_REPEAT when another participant of A stores i's hash.  pts and now ((sec, nsec) each,
+    given together or not at all): the pts the whole of A will be fed with and the clock then;
+    with them DIFF_APPLY says that SetElementByBinArray, meeting the matched blob as the existing
+    element, would not return early, and feed is the mask of the blobs worth feeding,
+    PART and (REPEAT or (APPLY and (FOUND ? a segment differs : DATA))): feeding them leaves the
+    table that feeding all of A leaves, when B holds exactly the table's elements for A's
+    identities.  Held elements A does not mention are reported (seen == 0), never removed.
+    count: the four counts, which synchronises the stream once; with count=False the call is
+    asynchronous and they are None."""
+    torch = _torch()
+    na = _check_stream(a_blobs, a_off, torch)
+    nb = _check_stream(b_blobs, b_off, torch)
+    dev = a_blobs.device
+    if b_blobs.device != dev:
+        raise ValueError("the two streams are on different devices")
+    if (pts is None) != (now is None):
+        raise ValueError("pts and now are given together or not at all")
+    a_consider = _consider_arg(a_consider, na, dev, torch)
+    b_consider = _consider_arg(b_consider, nb, dev, torch)
+    rel = torch.empty(na, dtype=torch.uint8, device=dev)
+    match = torch.empty(na, dtype=torch.int64, device=dev) if want_match else None
+    seen = torch.empty(nb, dtype=torch.uint8, device=dev) if want_seen else None
+    counts = (ctypes.c_uint64 * 4)()
+    times = None
+    if pts is not None:
+        times = _native.DiffTimes(_native.Timespec(int(pts[0]), int(pts[1])), _native.Timespec(int(now[0]), int(now[1])))
+    full = lambda t: ctypes.c_void_p(t.data_ptr() or 1)  # noqa: E731
+    opt = lambda t, n: ctypes.c_void_p(t.data_ptr() or 1) if t is not None and n else None  # noqa: E731
+    rc = _native.batch_lib().k2h_amd_ralledata_diff(
+        full(a_blobs), a_blobs.numel(), _dev_ptr(a_off), na, opt(a_consider, na),
+        full(b_blobs), b_blobs.numel(), _dev_ptr(b_off), nb, opt(b_consider, nb),
+        ctypes.byref(times) if times is not None else None, full(rel), opt(match, na), opt(seen, nb),
+        ctypes.cast(counts, ctypes.POINTER(ctypes.c_uint64)) if count else None, _stream_handle(stream))
+    _native.check(rc)
+    feed = None
+    if times is not None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            differs = (rel & (DIFF_VAL | DIFF_SKEY | DIFF_ATTRS)) != 0
+            change = torch.where((rel & DIFF_FOUND) != 0, differs, (rel & DIFF_DATA) != 0)
+            feed = (((rel & DIFF_PART) != 0) & (((rel & DIFF_REPEAT) != 0) | (((rel & DIFF_APPLY) != 0) & change))
+                    ).to(torch.uint8)
+    c = [int(x) for x in counts] if count else [None] * 4
+    return Diff(rel, match, seen, c[0], c[1], c[2], c[3], feed)
+
+
 def route_ralledata(blobs, blob_off, hash_range: HashRange, std_fnv: bool = False, stream=None,
                     dedup: bool = False, window: Optional[TimeWindow] = None, pts=None):
     """What a receiver that owns `hash_range` does with a stream: check it, then keep the
