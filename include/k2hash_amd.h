@@ -67,7 +67,12 @@ const char* k2h_hash_version(void);                         /* lib/k2hashfunc.h:
  * Per-key results follow the plugin semantics above; a key of length 0 hashes
  * to 0 (h1 and h2), and so does every key when the byte buffer is NULL.
  * h2 may be NULL (second hash not wanted).  `stream` is a hipStream_t
- * (NULL = the null stream); device-pointer calls are asynchronous on it.
+ * (NULL = the null stream).  Every device operation of a device-pointer call --
+ * kernels, memsets, copies -- is issued to `stream` and to no other, so inputs
+ * need only be ready on it; the call is asynchronous on it unless its section
+ * says how often it synchronises `stream`.  Host structs passed by pointer are
+ * read before the call returns.  (The Python wrappers order their own torch ops
+ * on `stream` as well; stream=None there is the current torch stream.)
  * ------------------------------------------------------------------------- */
 #define K2H_AMD_OK 0
 #define K2H_AMD_EINVAL (-1)   /* bad argument (NULL output, overflow, ...) */

@@ -212,8 +212,9 @@ def compact_device(file, stream=None) -> Compacted:
     if n == 0:
         return Compacted(file[:0].clone(), torch.empty(0, dtype=torch.int64, device=file.device), 0, 0, 0)
     rec_off = torch.empty(n + 1, dtype=torch.int64, device=file.device)
-    rec_off[:n] = recs[:, 1]
-    rec_off[n] = recs[n - 1, 1] + _native.K2H_AMD_SCOM_HEADER + recs[n - 1, 3:12:2].sum()
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        rec_off[:n] = recs[:, 1]
+        rec_off[n] = recs[n - 1, 1] + _native.K2H_AMD_SCOM_HEADER + recs[n - 1, 3:12:2].sum()
     sel = select_ralledata(file, rec_off, folded.keep, stream=stream)
     return Compacted(sel.blobs, sel.index, sel.kept, sel.kept_bytes, n)
 

@@ -1,9 +1,17 @@
 """Batch key hashing on MI355X through the k2hash_amd C ABI.
 
-Device forms take torch tensors already resident in HBM and launch on the
-current torch stream; host forms take numpy arrays and use the library's
-pinned-staging pipeline.  Hashes are returned as int64 tensors/arrays holding
-the 64-bit k2h_hash_t bit patterns (view as uint64 with numpy for printing).
+Device forms take torch tensors already resident in HBM; host forms take numpy
+arrays and use the library's pinned-staging pipeline.  Hashes are returned as
+int64 tensors/arrays holding the 64-bit k2h_hash_t bit patterns (view as uint64
+with numpy for printing).
+
+The `stream` argument, here and in archive.py and ralledata.py: stream=None means
+the current torch stream.  Otherwise every device operation of the call -- kernels,
+memsets, read-backs and the wrapper's own torch ops -- is ordered on `stream`, and
+none on the current stream: inputs need only be ready on `stream`, and a busy
+current stream is neither waited for nor used.  Outputs are allocated from the
+current stream's pool; a caller who drops them while `stream` still works on them
+must order that itself (torch.Tensor.record_stream, or a synchronisation).
 """
 from __future__ import annotations
 
@@ -388,8 +396,10 @@ def synth_offsets(n: int, device, min_len: int = 8, max_len: int = 256, seed: in
     rc = _native.batch_lib().k2h_amd_synth_lengths(_dev_ptr(lens), n, seed, first_key, min_len, max_len,
                                                     _stream_handle(stream))
     _native.check(rc)
-    off = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    torch.cumsum(lens, dim=0, dtype=torch.int64, out=off[1:])
+    off = torch.empty(n + 1, dtype=torch.int64, device=device)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        off[:1] = 0
+        torch.cumsum(lens, dim=0, dtype=torch.int64, out=off[1:])
     return off
 
 

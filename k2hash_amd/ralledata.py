@@ -48,10 +48,12 @@ def ralledata_size(n: int, key_bytes: int, val_bytes: int = 0, skey_bytes: int =
     return int(_native.batch_lib().k2h_amd_ralledata_size(n, key_bytes, val_bytes, skey_bytes, attr_bytes))
 
 
-def _seg_bytes(off) -> int:
+def _seg_bytes(off, stream=None) -> int:
     if off is None or off.numel() == 0:
         return 0
-    return int(off[-1].item()) - int(off[0].item())
+    torch = _torch()
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        return int(off[-1].item()) - int(off[0].item())
 
 
 def build_ralledata(keys, key_off, vals=None, val_off=None, skeys=None, skey_off=None, attrs=None, attr_off=None,
@@ -76,7 +78,7 @@ def build_ralledata(keys, key_off, vals=None, val_off=None, skeys=None, skey_off
         _check_dev(o, f"{name} offsets", torch.int64)
         _check_dev(b, name, torch.uint8)
         args += [ctypes.c_void_p(b.data_ptr() or 1), _dev_ptr(o)]
-        nbytes.append(0 if total is not None and out is not None else _seg_bytes(o))
+        nbytes.append(0 if total is not None and out is not None else _seg_bytes(o, stream))
     if total is None or out is None:
         total = ralledata_size(n, *nbytes)
     elif out.numel() < total:
@@ -351,7 +353,8 @@ def partition_ralledata(blobs, blob_off, parts: int, *, ids=None, owner=None, ma
     _native.check(call(_dev_ptr(out), out.numel(), _dev_ptr(out_off), opt(index), opt(part_of)))
     k, kb = int(first[parts]), int(byte[parts])
     if n == 0:
-        out_off[:1] = 0
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            out_off[:1] = 0
     return Partitioned(out[:kb], out_off[:k + 1], index[:k] if want_index else None, part_of, list(first), list(byte),
                        k, kb)
 
@@ -596,11 +599,11 @@ def diff_ralledata(a_blobs, a_off, b_blobs, b_off, a_consider=None, b_consider=N
     _native.check(rc)
     feed = None
     if times is not None:
+        feed = torch.empty(na, dtype=torch.uint8, device=dev)  # as every output: from the current stream's pool
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
             differs = (rel & (DIFF_VAL | DIFF_SKEY | DIFF_ATTRS)) != 0
             change = torch.where((rel & DIFF_FOUND) != 0, differs, (rel & DIFF_DATA) != 0)
-            feed = (((rel & DIFF_PART) != 0) & (((rel & DIFF_REPEAT) != 0) | (((rel & DIFF_APPLY) != 0) & change))
-                    ).to(torch.uint8)
+            feed.copy_(((rel & DIFF_PART) != 0) & (((rel & DIFF_REPEAT) != 0) | (((rel & DIFF_APPLY) != 0) & change)))
     c = [int(x) for x in counts] if count else [None] * 4
     return Diff(rel, match, seen, c[0], c[1], c[2], c[3], feed)
 
