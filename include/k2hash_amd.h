@@ -580,6 +580,137 @@ int k2h_amd_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t*
                            uint64_t nb, const uint8_t* b_consider, const k2h_amd_diff_times* times, uint8_t* rel,
                            uint64_t* match, uint8_t* seen, uint64_t* counts, void* stream);
 
+/* 4b''''''. Subkeys followed through a stream: edges and subtree closure.  Every call above
+ * treats a blob's subkeys segment as opaque bytes, yet subkeys are what make a k2hash table a
+ * tree: K2HShm::Remove(key, true) removes a key with everything below it.  These two calls read
+ * the segment: _subkeys turns every name in it into an edge to the blob the table would find
+ * under that name, _reach follows the edges from a set of roots.  Device pointers except
+ * `counts`.
+ *
+ * The segment, K2HSubKeys::Serialize(const unsigned char*, size_t), lib/k2hsubkeys.cc:113-156,
+ * with S the segment and L = skeys_length: a u64 count, then count entries of u64 length +
+ * length bytes.  A zero-length entry is refused by insert (:302-305) and skipped, parsing goes
+ * on; when a length field or a name does not fit, Serialize returns false and
+ * K2HPage::GetSubKeys throws the whole list away (lib/k2hpage.cc:274-299): a rejected segment
+ * means no subkeys, not the entries read so far.  Bytes after the last entry are ignored;
+ * count == 0 is an accepted empty list.  One departure, the counterpart of the one section
+ * 4b'''' makes for the attrs sum that wraps: the reference starts rest_length at the whole L although its read
+ * position is already past the count, so on a malformed segment it accepts an entry that runs
+ * up to 8 bytes past the segment's end, and it reads the count out of bounds when L is 1 to 7.
+ * The rule here is the strict one, which never reads outside the segment: L == 0 is no list;
+ * L < 8 is BAD; else pos = 8 and count times: BAD if L - pos < 8; len = the u64 at pos,
+ * pos += 8; BAD if L - pos < len; an edge when len > 0; pos += len.  Every segment the
+ * reference's own writer produces is judged the same by both rules; they differ only where the
+ * reference reads out of bounds.
+ *
+ * The rule restated, K2HShm::Remove(key, true): lib/k2hshm.cc:2544-2560, RemoveEx :2735-2864,
+ * RemoveSubkeys :2866-2898.  It hashes the name with K2H_HASH_FUNC / K2H_2ND_HASH_FUNC, finds
+ * the element by hash, subhash and key bytes, takes its subkey list through
+ * GetSubKeys(pElement, pSubKeys) -- the form that makes no expiry or history check -- removes
+ * the element, and does the same for every name in the list, re-entrantly; a name that is not
+ * found is skipped, and a cycle ends because the element is already gone.  The history
+ * attribute (IsMarkHistory), which renames instead of removing, is out of scope.
+ *
+ * Proviso.  "The table the stream leaves" is taken as: the LAST participant of an identity
+ * wins.  That holds for a feed without the mtime attribute or with non-decreasing times; a
+ * caller with mtime-bearing blobs passes as `consider` the keep of k2h_amd_ralledata_dedup_mtime
+ * first.  Expiry is deliberately not applied, as Remove does not apply it; a caller who wants
+ * it composes k2h_amd_ralledata_times.  A participant with a key and nothing else counts as its
+ * key's last copy like any other, although feeding it leaves no element (lib/k2hshmdirect.cc:438):
+ * it has no list, and a name that addresses it is not dangling.
+ *
+ * k2h_amd_ralledata_subkeys.  Participants, as _dedup: consider is NULL or consider[i] != 0,
+ * the span is good and the header is not EMPTY, NO_KEY or BAD_RANGE.  An edge carries the
+ * name's COMPUTED hashes -- k2h_hash and k2h_second_hash over the raw name bytes, no NUL added
+ * (the name carries whatever NUL it was stored with), seed by K2H_AMD_FLAG_STD_FNV -- its length
+ * and its bytes; a blob its STORED hash, stored subhash, key_length and key bytes (the identity
+ * of section 4b').  They are joined as the table would look the name up: a blob whose stored
+ * hashes are wrong is not found by name.
+ *
+ *   sk_flags[i] (n, required) 0 for a non-participant; else K2H_AMD_SKEY_PART, _HAS when
+ *               skeys_length != 0, _BAD when the strict walk rejected the segment (then no edges)
+ *   edge_off    (n + 1, required) edge_off[0] = 0; blob i's edges are [edge_off[i],
+ *               edge_off[i+1]), one per entry with len > 0 in segment order; E = edge_off[n]
+ *   rep[i]      (n, may be NULL) the LAST participant of i's own identity: i itself for the last
+ *               copy of a key; ~0 for a non-participant.  Written only when child != NULL.
+ *   child[e]    (cap entries; NULL: count only) the LAST participant whose identity edge e's name
+ *               addresses; ~0 when there is none: a dangling name
+ *   counts      (host, 5 entries, required) participants, blobs with >= 1 edge, BAD segments,
+ *               E, dangling edges (0 when child is NULL)
+ *
+ * `stream` is synchronised once after the count pass (E sizes everything behind it) and, when
+ * child != NULL, once more at the end: once with child NULL, twice otherwise.  No form of the
+ * call is asynchronous.
+ *
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ * counts NULL; K2H_AMD_FLAG_CSTR; unknown flag bits; sk_flags, edge_off, blobs or blob_off NULL
+ * with n > 0; n > 2^32 - 2.  After the count pass, with counts and edge_off filled and nothing
+ * written to child or rep: child != NULL and cap < E (the message names E); n + E > 2^32 - 2
+ * (blobs and edges are sorted as 32-bit indices of one space, as in _diff).  n == 0:
+ * K2H_AMD_OK, counts zeroed, edge_off[0] = 0 by one memset on `stream` (when edge_off is given).
+ *
+ * No byte outside [0, size) is read except within the aligned 16 bytes that hold a valid byte;
+ * every load of the walk lies inside the subkeys segment, at any alignment; nothing of a
+ * non-participant beyond its header, and nothing outside a blob's own subkeys segment is ever
+ * interpreted.  All absolute offsets are 64-bit.
+ *
+ * Cost: a count pass over the headers and the segments (one lane walks one segment: one
+ * dependent 8-byte load per entry, so a very long list holds its wave for its length); with
+ * child a second such pass that leaves the names' places, a pass that hashes every name, one
+ * library radix sort of n + E (hash, index) pairs on the hash's low bits, two max-scans and a
+ * resolve pass that reads the keys and names whose hashes meet.  r copies of one key cost O(1)
+ * steps per entry; r DISTINCT identities that agree in all sorted bits cost O(r) steps per
+ * entry among them -- the crafted-stream case of section 4b'.  Temporary device memory, kept
+ * per device between calls and shared with _reach: 60 bytes per blob and edge of n + E, a byte
+ * and the tile counts per blob, plus the sort's own; count only: 8 bytes per blob.
+ *
+ * k2h_amd_ralledata_reach.  edge_off, child and rep are the outputs of _subkeys over the same
+ * n (trusted as such; a child or rep entry >= n is taken as ~0); roots is a byte per blob.
+ * Start set: {rep[i] : roots[i] != 0, rep[i] != ~0} -- a root that is an earlier copy of a key
+ * stands for the key's last copy, a root that is a non-participant for nothing.  A
+ * level-synchronous frontier traversal follows child from there.  Only blobs that are their own
+ * rep are followed: earlier copies of a key are not in the table, and their lists do not exist.
+ * A blob is visited once; total work is O(n + E).
+ *
+ *   reach[i]  (n, required) rep[i] != ~0 and rep[i] was visited: every copy of a reached key is
+ *             marked, so keep = ~reach cannot resurrect a removed key from an earlier duplicate
+ *   counts    (host, 3 entries, required) blobs with reach 1; levels run; converged (1 or 0)
+ *   max_levels  0: no limit.  Else at most that many levels are run; when the frontier is not
+ *             empty then, converged is 0 and reach marks a subset of the closure.
+ *
+ * A level is one kernel over the current frontier and one 8-byte read-back of the next
+ * frontier's size through pinned host memory.  `stream` is synchronised once for the start
+ * set, once per level run and once at the end: levels + 2 times.  A chain-shaped stream (every
+ * blob naming the next) costs one level per link: the crafted case, which max_levels bounds.
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ * counts NULL; with n > 0: reach, edge_off, child, rep or roots NULL; n > 2^32 - 2.  n == 0:
+ * K2H_AMD_OK, counts = 0, 0, 1, no device work.  Temporary device memory: a bit and 8 bytes per
+ * blob.
+ *
+ * Parity: the parse is pinned by tests/golden/ralle_subkeys.json, written by the reference's
+ * own K2HSubKeys (tests/golden/gen_ralle_subkeys.cc); Remove is a restatement
+ * (tests/ralle_subkeys_model.py) -- libk2hash itself is not built by this project's tests. */
+#define K2H_AMD_SKEY_PART 0x1u   /* participant */
+#define K2H_AMD_SKEY_HAS  0x2u   /* skeys_length != 0 */
+#define K2H_AMD_SKEY_BAD  0x4u   /* HAS, and the strict walk rejected the segment: no edges */
+
+int k2h_amd_ralledata_subkeys(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                              const uint8_t* consider, uint32_t flags,
+                              uint8_t* sk_flags,      /* n, required */
+                              uint64_t* edge_off,     /* n+1, required */
+                              uint64_t* rep,          /* n, may be NULL */
+                              uint64_t* child,        /* cap entries; NULL: count only */
+                              uint64_t cap,
+                              uint64_t* counts,       /* host, required: participants, blobs with >= 1 edge,
+                                                         BAD segments, edges E, dangling edges (0 when child NULL) */
+                              void* stream);
+
+int k2h_amd_ralledata_reach(const uint64_t* edge_off, const uint64_t* child, const uint64_t* rep, uint64_t n,
+                            const uint8_t* roots, uint64_t max_levels,
+                            uint8_t* reach,           /* n, required */
+                            uint64_t* counts,         /* host, required: blobs reached, levels run, converged (0/1) */
+                            void* stream);
+
 /* 4c. Blobs straight from scanned records: the middle of a bulk load whose file is already
  * in device memory.  The device scans of section 5 (k2h_amd_import_scan_device,
  * k2h_amd_archive_scan_device and their _scan_prehash_device forms) report every record as

@@ -83,6 +83,8 @@ class DiffTimes(ctypes.Structure):
 K2H_AMD_DIFF_PART, K2H_AMD_DIFF_FOUND, K2H_AMD_DIFF_VAL, K2H_AMD_DIFF_SKEY = 0x01, 0x02, 0x04, 0x08
 K2H_AMD_DIFF_ATTRS, K2H_AMD_DIFF_DATA, K2H_AMD_DIFF_REPEAT, K2H_AMD_DIFF_APPLY = 0x10, 0x20, 0x40, 0x80
 
+K2H_AMD_SKEY_PART, K2H_AMD_SKEY_HAS, K2H_AMD_SKEY_BAD = 0x1, 0x2, 0x4
+
 _twp = ctypes.POINTER(TimeWindowStruct)
 _dtp = ctypes.POINTER(DiffTimes)
 _tsp = ctypes.POINTER(Timespec)
@@ -113,6 +115,9 @@ SIGNATURES = {
     "k2h_amd_ralledata_dedup_mtime": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _tsp, _p]),
     "k2h_amd_ralledata_diff": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _p, _dtp, _p, _p, _p, _u64p,
                                               _p]),
+    "k2h_amd_ralledata_subkeys": (ctypes.c_int, [_p, _u64, _p, _u64, _p, ctypes.c_uint32, _p, _p, _p, _p, _u64, _u64p,
+                                                 _p]),
+    "k2h_amd_ralledata_reach": (ctypes.c_int, [_p, _p, _p, _u64, _p, _u64, _p, _u64p, _p]),
     "k2h_amd_ralledata_partition": (ctypes.c_int, [_p, _u64, _p, _u64, _prp, _p, _p, _p, _u64, _p, _p, _p, _u64p,
                                                    _u64p, _p]),
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),

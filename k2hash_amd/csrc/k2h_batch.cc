@@ -928,6 +928,70 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_diff(
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_diff", e);
 }
 
+// Section 4b'''''': subkeys as edges, and the subtree closure.  Judged on the host like the ones above.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_subkeys(
+    const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const uint8_t* consider, uint32_t flags,
+    uint8_t* sk_flags, uint64_t* edge_off, uint64_t* rep, uint64_t* child, uint64_t cap, uint64_t* counts,
+    void* stream) {
+  if (!counts) return fail(K2H_AMD_EINVAL, "ralledata_subkeys: NULL counts");
+  for (int k = 0; k < 5; ++k) counts[k] = 0;
+  if (flags & K2H_AMD_FLAG_CSTR)
+    return fail(K2H_AMD_EINVAL, "ralledata_subkeys: subkey names are hashed as stored");
+  if (flags & ~(uint32_t)K2H_AMD_FLAG_STD_FNV) return fail(K2H_AMD_EINVAL, "ralledata_subkeys: unknown flag bits");
+  if (n && !sk_flags) return fail(K2H_AMD_EINVAL, "ralledata_subkeys: NULL sk_flags");
+  if (n && !edge_off) return fail(K2H_AMD_EINVAL, "ralledata_subkeys: NULL edge_off");
+  if (n && !blobs) return fail(K2H_AMD_EINVAL, "ralledata_subkeys: NULL blobs");
+  if (n && !blob_off) return fail(K2H_AMD_EINVAL, "ralledata_subkeys: NULL blob_off");
+  if (n > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL,
+                "ralledata_subkeys: more than 2^32 - 2 blobs and edges (indices are sorted as 32-bit values)");
+  if (n == 0 && !edge_off) return K2H_AMD_OK;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  if (n == 0) {  // no blob, no edge: edge_off[0] = 0
+    e = hipMemsetAsync(edge_off, 0, 8, (hipStream_t)stream);
+    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_subkeys: hipMemsetAsync", e);
+  }
+  int why = 0;
+  int rc = k2h::launch_ralledata_subkeys(blobs, size, blob_off, n, consider, seed_for(flags), sk_flags, edge_off, rep,
+                                         child, cap, counts, &why, (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EINVAL) {
+    char msg[160];
+    if (why == 1)
+      snprintf(msg, sizeof msg, "ralledata_subkeys: cap %llu is less than the E = %llu edges of the stream",
+               (unsigned long long)cap, (unsigned long long)counts[3]);
+    else
+      snprintf(msg, sizeof msg,
+               "ralledata_subkeys: more than 2^32 - 2 blobs and edges (n + E with E = %llu; indices are sorted as "
+               "32-bit values)",
+               (unsigned long long)counts[3]);
+    return fail(rc, msg);
+  }
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_subkeys", e);
+}
+
+__attribute__((visibility("default"))) int k2h_amd_ralledata_reach(const uint64_t* edge_off, const uint64_t* child,
+                                                                   const uint64_t* rep, uint64_t n,
+                                                                   const uint8_t* roots, uint64_t max_levels,
+                                                                   uint8_t* reach, uint64_t* counts, void* stream) {
+  if (!counts) return fail(K2H_AMD_EINVAL, "ralledata_reach: NULL counts");
+  counts[0] = counts[1] = 0;
+  counts[2] = 1;  // nothing to traverse: converged
+  if (n == 0) return K2H_AMD_OK;
+  if (!reach) return fail(K2H_AMD_EINVAL, "ralledata_reach: NULL reach");
+  if (!edge_off) return fail(K2H_AMD_EINVAL, "ralledata_reach: NULL edge_off");
+  if (!child) return fail(K2H_AMD_EINVAL, "ralledata_reach: NULL child");
+  if (!rep) return fail(K2H_AMD_EINVAL, "ralledata_reach: NULL rep");
+  if (!roots) return fail(K2H_AMD_EINVAL, "ralledata_reach: NULL roots");
+  if (n > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL, "ralledata_reach: more than 2^32 - 2 blobs (a frontier holds 32-bit indices)");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_ralledata_reach(edge_off, child, rep, n, roots, max_levels, reach, counts, (hipStream_t)stream,
+                                       &e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_reach", e);
+}
+
 // Section 4b'': the stream split into parts.  Judged on the host like the three above.
 __attribute__((visibility("default"))) int k2h_amd_ralledata_partition(
     const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const k2h_amd_part_rule* rule,

@@ -143,6 +143,20 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
                           uint64_t nb, const uint8_t* b_consider, const k2h_amd_diff_times* times, uint8_t* rel,
                           uint64_t* match, uint8_t* seen, uint64_t* counts, hipStream_t stream, hipError_t* herr);
 
+// The subkeys of a stream as edges between its blobs, and what root blobs reach over them
+// (k2h_ralledata_subkeys.hip).  Both return a K2H_AMD_* code (the HIP error in *herr);
+// 1 <= n <= 2^32 - 2.  _subkeys synchronises the stream once after its count pass and, when
+// child != NULL, once more at the end; K2H_AMD_EINVAL with *why = 1: cap < E, 2: n + E >
+// 2^32 - 2 (counts and edge_off are filled, child is not written).  _reach synchronises once for
+// the start set, once per level run and once at the end.
+int launch_ralledata_subkeys(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                             const uint8_t* consider, uint64_t seed, uint8_t* sk_flags, uint64_t* edge_off,
+                             uint64_t* rep, uint64_t* child, uint64_t cap, uint64_t* counts, int* why,
+                             hipStream_t stream, hipError_t* herr);
+int launch_ralledata_reach(const uint64_t* edge_off, const uint64_t* child, const uint64_t* rep, uint64_t n,
+                           const uint8_t* roots, uint64_t max_levels, uint8_t* reach, uint64_t* counts,
+                           hipStream_t stream, hipError_t* herr);
+
 // The mtime and expire of every blob's attrs and the time-window selection
 // (k2h_ralledata_times.hip).  Asynchronous on the stream; n >= 1, window may be NULL.
 hipError_t launch_ralledata_times(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,

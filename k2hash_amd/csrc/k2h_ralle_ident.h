@@ -1,12 +1,22 @@
 // k2hash_amd -- a blob's identity as the kernels that sort blobs by their stored hash hold and
-// compare it (k2h_ralledata_dedup.hip, k2h_ralledata_diff.hip): the side record a gather leaves
-// per participant, the end-aligned 16-byte compare of two byte ranges of one length, and the
-// number of hash bits the pairs are sorted by.
+// compare it (k2h_ralledata_dedup.hip, k2h_ralledata_diff.hip, k2h_ralledata_subkeys.hip): the
+// side record a gather leaves per participant, the end-aligned 16-byte compare of two byte ranges
+// of one length, and the number of hash bits the pairs are sorted by.  Below those, the join's
+// machinery in the form k2h_ralledata_subkeys.hip launches it: the kernel that lays the pairs
+// out for the sort, the mark kernel and max-scan operator, the backward walk to the last held
+// entry of an identity, and the per-device scratch.  k2h_ralledata_dedup.hip and
+// k2h_ralledata_diff.hip, from which these were lifted, keep their own copies for now (see
+// DESIGN.md 5.4i).
 #pragma once
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <stddef.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "k2h_endwalk.h"
+#include "k2h_kernels.h"
 
 namespace k2h {
 
@@ -38,6 +48,11 @@ __device__ __forceinline__ bool same_key(const uint8_t* a, const uint8_t* b, uin
   return true;
 }
 
+__device__ __forceinline__ uint64_t ralle_shfl_u64(uint64_t v, int src) {
+  const uint32_t lo = __shfl((uint32_t)v, src), hi = __shfl((uint32_t)(v >> 32), src);
+  return pack2(lo, hi);
+}
+
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The low hash bits the pairs are sorted by: 8 more than the blobs' number has, in whole
@@ -51,5 +66,99 @@ inline int sort_bits_for(uint64_t n) {
   bits = (bits + 8 + 7) / 8 * 8;
   return bits < 16 ? 16 : bits > 64 ? 64 : bits;
 }
+
+constexpr int kIdentBlobs = 256;  // gather / compact: blobs per 256-thread block, one per thread
+
+// The sort's input: participant g at its rank among the participants, every other blob behind
+// all m of them and behind `extra` more places that the caller fills itself, as (~0, kNone) --
+// so a non-participant sorts behind every participant of any hash and ends every walk that
+// reaches it (tile_base = the scanned tile counts, entry ntiles = m).
+// (A template only so that every file that launches it holds its own copy.)
+template <int BLOBS = kIdentBlobs>
+__global__ __launch_bounds__(BLOBS) void ralle_compact_kernel(const uint8_t* __restrict__ part,
+                                                              const uint64_t* __restrict__ hash, uint64_t n,
+                                                              const uint64_t* __restrict__ tile_base, uint64_t ntiles,
+                                                              uint64_t extra, uint64_t* __restrict__ keys,
+                                                              uint32_t* __restrict__ idx) {
+  typedef hipcub::BlockScan<uint32_t, BLOBS> Scan;
+  __shared__ typename Scan::TempStorage tmp;
+  const uint64_t g = (uint64_t)blockIdx.x * BLOBS + threadIdx.x;
+  const uint32_t p = g < n && part[g] ? 1u : 0u;
+  uint32_t rank;
+  Scan(tmp).ExclusiveSum(p, rank);
+  if (g >= n) return;
+  const uint64_t before = tile_base[blockIdx.x] + rank;  // participants before blob g
+  const uint64_t pos = p ? before : tile_base[ntiles] + extra + (g - before);
+  keys[pos] = p ? hash[g] : ~0ull;
+  idx[pos] = p ? (uint32_t)g : kNone;
+}
+
+// mark[p] = p + 1 for a sorted entry with an index below nb (a held blob), else 0: the
+// max-scan's input.
+template <int BLOCK = 256>
+__global__ __launch_bounds__(BLOCK) void ralle_mark_kernel(const uint32_t* __restrict__ idx, uint64_t n, uint64_t nb,
+                                                           uint32_t* __restrict__ mark) {
+  const uint64_t p = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (p < n) mark[p] = idx[p] < nb ? (uint32_t)(p + 1) : 0u;
+}
+
+struct RalleMaxU32 {
+  __host__ __device__ __forceinline__ uint32_t operator()(uint32_t x, uint32_t y) const { return x > y ? x : y; }
+};
+
+// The last held entry (index below nb) with the identity of `sa` and hash h: backward from
+// sorted position q0 (1 + a position, 0: none) over the run's held entries while the sorted
+// bits agree.  Returns its index and leaves its side record in sb; kNone when there is none.
+// x: the buffer sa's key offset counts from, y: the held entries'.
+__device__ __forceinline__ uint32_t last_held(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                              const Side* __restrict__ side, uint64_t q0, uint64_t h, uint64_t mask,
+                                              uint64_t nb, const Side& sa, const uint8_t* x, const uint8_t* y,
+                                              Side& sb) {
+  for (uint64_t q = q0; q > 0; --q) {
+    const uint64_t hq = keys[q - 1];
+    if ((hq ^ h) & mask) break;
+    if (hq != h) continue;  // another hash with the same sorted bits
+    const uint32_t c = idx[q - 1];
+    if (c >= nb) break;  // (never: in a run every entry before a held entry is held)
+    const Side sc = side[c];
+    if (sc.sub != sa.sub || sc.klen != sa.klen || !same_key(x + sa.koff, y + sc.koff, sa.klen)) continue;
+    sb = sc;
+    return c;
+  }
+  return kNone;
+}
+
+// A launcher's temporaries: one grow-only buffer per device, held across calls under a
+// per-device lock.  The kernels still use the buffer after an asynchronous call has returned,
+// so each call leaves an event behind and the next call's stream waits for it before it writes.
+struct RalleScratch {
+  std::mutex mu;
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t done = nullptr;
+  // Under mu: at least `total` bytes at p, and `stream` behind the last call's event.  Returns
+  // a K2H_AMD_* code (the HIP error in *herr).
+  int reserve(size_t total, hipStream_t stream, hipError_t* herr) {
+    hipError_t e = hipSuccess;
+    if (!done) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+    if (e == hipSuccess && bytes < total) {
+      if (p) e = hipFree(p);  // waits for the device: no earlier call's kernel still uses it
+      p = nullptr;
+      bytes = 0;
+      const hipError_t a = e == hipSuccess ? hipMalloc(&p, total) : e;
+      if (a == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        p = nullptr;
+        *herr = a;
+        return K2H_AMD_ENOMEM;
+      }
+      if (e == hipSuccess) e = a;
+      if (e == hipSuccess) bytes = total;
+    }
+    if (e == hipSuccess) e = hipStreamWaitEvent(stream, done, 0);  // never recorded: no wait
+    *herr = e;
+    return e == hipSuccess ? K2H_AMD_OK : K2H_AMD_EHIP;
+  }
+};
 
 }  // namespace k2h
