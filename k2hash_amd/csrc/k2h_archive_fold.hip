@@ -262,7 +262,7 @@ __global__ __launch_bounds__(kFoldRecs) void archive_fold_finish_kernel(const ui
 
 // The call's temporaries: one grow-only buffer per device, held across calls under a
 // per-device lock, with an event the next call's stream waits for (the pattern of
-// DedupScratch, k2h_ralledata_dedup.hip) -- 72 bytes per record (two key and two index
+// RalleScratch, k2h_ralle_ident.h) -- 72 bytes per record (two key and two index
 // columns, the side records, two summary columns), the tile counts and their scan, the round
 // flags, the counters, and the library's own storage.
 struct FoldScratch {

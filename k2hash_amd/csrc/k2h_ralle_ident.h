@@ -5,8 +5,7 @@
 // machinery in the form k2h_ralledata_subkeys.hip launches it: the kernel that lays the pairs
 // out for the sort, the mark kernel and max-scan operator, the backward walk to the last held
 // entry of an identity, and the per-device scratch.  k2h_ralledata_dedup.hip and
-// k2h_ralledata_diff.hip, from which these were lifted, keep their own copies for now (see
-// DESIGN.md 5.4i).
+// k2h_ralledata_diff.hip, from which these were lifted, launch the same ones.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -108,12 +107,15 @@ struct RalleMaxU32 {
 
 // The last held entry (index below nb) with the identity of `sa` and hash h: backward from
 // sorted position q0 (1 + a position, 0: none) over the run's held entries while the sorted
-// bits agree.  Returns its index and leaves its side record in sb; kNone when there is none.
-// x: the buffer sa's key offset counts from, y: the held entries'.
+// bits agree.  Returns its index, kNone when there is none.  x: the buffer sa's key offset counts
+// from, y: the held entries'.  The walk hands out the index only: a caller that needs the held
+// entry's side record reads side[index] behind the walk.  A record carried out of the loop was
+// seen to keep the caller's initial value for keys of more than 16 bytes in one build of
+// k2h_ralledata_diff.hip, and the index alone also leaves the loop fewer
+// registers to keep.
 __device__ __forceinline__ uint32_t last_held(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
                                               const Side* __restrict__ side, uint64_t q0, uint64_t h, uint64_t mask,
-                                              uint64_t nb, const Side& sa, const uint8_t* x, const uint8_t* y,
-                                              Side& sb) {
+                                              uint64_t nb, const Side& sa, const uint8_t* x, const uint8_t* y) {
   for (uint64_t q = q0; q > 0; --q) {
     const uint64_t hq = keys[q - 1];
     if ((hq ^ h) & mask) break;
@@ -122,7 +124,6 @@ __device__ __forceinline__ uint32_t last_held(const uint64_t* __restrict__ keys,
     if (c >= nb) break;  // (never: in a run every entry before a held entry is held)
     const Side sc = side[c];
     if (sc.sub != sa.sub || sc.klen != sa.klen || !same_key(x + sa.koff, y + sc.koff, sa.klen)) continue;
-    sb = sc;
     return c;
   }
   return kNone;

@@ -119,25 +119,6 @@ __global__ __launch_bounds__(256) void ralledata_dedup_gather_kernel(
   if (threadIdx.x == 0) tile_count[blockIdx.x] = count;
 }
 
-// The sort's input, n pairs: participant i at its rank among the participants, every other
-// blob behind all m of them (tile_base = the scanned tile counts, entry ntiles = m).
-__global__ __launch_bounds__(256) void ralledata_dedup_compact_kernel(
-    const uint8_t* __restrict__ keep, const uint64_t* __restrict__ hash, uint64_t n,
-    const uint64_t* __restrict__ tile_base, uint64_t ntiles, uint64_t* __restrict__ keys,
-    uint32_t* __restrict__ idx) {
-  typedef hipcub::BlockScan<uint32_t, kDedupBlobs> Scan;
-  __shared__ typename Scan::TempStorage tmp;
-  const uint64_t i = (uint64_t)blockIdx.x * kDedupBlobs + threadIdx.x;
-  const uint32_t part = i < n && keep[i] ? 1u : 0u;
-  uint32_t rank;
-  Scan(tmp).ExclusiveSum(part, rank);
-  if (i >= n) return;
-  const uint64_t before = tile_base[blockIdx.x] + rank;  // participants before blob i
-  const uint64_t pos = part ? before : tile_base[ntiles] + (i - before);
-  keys[pos] = part ? hash[i] : ~0ull;
-  idx[pos] = part ? (uint32_t)i : kNone;
-}
-
 // keys / idx: the pairs, sorted by the hash bits under `mask` (sort_bits_for).  Writes
 // keep[i] = 0 for a superseded blob and by[i] for every blob that has a later one of its
 // identity; counts the superseded into the kCounters words of `dropped` (their sum is the
@@ -188,20 +169,11 @@ __global__ __launch_bounds__(kResolveBlock) void ralledata_dedup_resolve_kernel(
   }
 }
 
-// The call's temporaries: one grow-only buffer per device, held across calls under a
-// per-device lock (the pattern of SelScratch, k2h_ralledata_check.hip) -- 56 bytes per blob
-// (two key and two index columns, the side records), the tile counts and their scan, the
-// counters, and the library's own storage; the mtime rule adds 16 bytes per blob behind
-// them.  The kernels still use the buffer after an
-// asynchronous call has returned, so each call leaves an event behind and the next call's
-// stream waits for it before it writes.
-struct DedupScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-};
-DedupScratch g_dedup[64];
+// The call's temporaries (RalleScratch, k2h_ralle_ident.h: one grow-only buffer per device under
+// a lock, with the event the next call's stream waits for) -- 56 bytes per blob (two key and two
+// index columns, the side records), the tile counts and their scan, the counters, and the
+// library's own storage; the mtime rule adds 16 bytes per blob behind them.
+RalleScratch g_dedup[64];
 
 constexpr size_t kCounterBytes = 64 * kCounters;
 
@@ -235,28 +207,9 @@ int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uin
   const size_t tmp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
   const size_t cm = pts ? align256(n * sizeof(Mtime)) : 0;  // behind everything else: the plain rule's layout stays
   const size_t total = 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes + align256(tmp_bytes) + cm;
-  DedupScratch& sc = g_dedup[dev];
+  RalleScratch& sc = g_dedup[dev];
   std::lock_guard<std::mutex> lk(sc.mu);
-  if (!sc.done) tr(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-  if (e == hipSuccess && sc.bytes < total) {
-    if (sc.p) tr(hipFree(sc.p));  // waits for the device: no earlier call's kernel still uses it
-    sc.p = nullptr;
-    sc.bytes = 0;
-    const hipError_t a = e == hipSuccess ? hipMalloc(&sc.p, total) : e;
-    if (a == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      sc.p = nullptr;
-      *herr = a;
-      return K2H_AMD_ENOMEM;
-    }
-    tr(a);
-    if (e == hipSuccess) sc.bytes = total;
-  }
-  if (e == hipSuccess) tr(hipStreamWaitEvent(stream, sc.done, 0));  // never recorded: no wait
-  if (e != hipSuccess) {
-    *herr = e;
-    return K2H_AMD_EHIP;
-  }
+  if (const int rc = sc.reserve(total, stream, herr)) return rc;
   uint8_t* base = (uint8_t*)sc.p;
   uint64_t* keys_in = (uint64_t*)base;
   uint64_t* keys_out = (uint64_t*)(base + c8);  // first the blobs' hashes by blob index, then the sorted keys
@@ -282,8 +235,8 @@ int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uin
   }
   if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, tile_count, tile_base, nt + 1, stream));
   if (e == hipSuccess) {
-    ralledata_dedup_compact_kernel<<<(unsigned)nt, kDedupBlobs, 0, stream>>>(keep, keys_out, n, tile_base, nt, keys_in,
-                                                                           idx_in);
+    ralle_compact_kernel<kDedupBlobs><<<(unsigned)nt, kDedupBlobs, 0, stream>>>(keep, keys_out, n, tile_base, nt, 0,
+                                                                               keys_in, idx_in);
     tr(hipGetLastError());
   }
   if (e == hipSuccess)

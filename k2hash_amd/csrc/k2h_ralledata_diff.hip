@@ -14,7 +14,7 @@
 //            a participant leaves its stored hash and a side record (k2h_ralle_ident.h) whose
 //            last word holds its flags; with times it also has its attrs walked
 //            (k2h_ralle_attrs.h) and leaves its mtime, and a blob of B whether it is expired
-//            at `now`.  A scan of the tiles' participant counts and a compact kernel lay the
+//            at `now`.  A scan of the tiles' participant counts and the compact kernel lay the
 //            (hash, index) pairs out for the sort, participants first in index order.
 //   sort     hipcub::DeviceRadixSort::SortPairs on the hash's low bits (sort_bits_for): stable,
 //            so within a run of equal sorted bits all of B's entries come first, in stream
@@ -140,37 +140,6 @@ __global__ __launch_bounds__(256) void ralledata_diff_gather_kernel(DiffStream a
   if (threadIdx.x == 0) tile_count[blockIdx.x] = count;
 }
 
-// The sort's input, n pairs: participant g at its rank among the participants, every other
-// blob behind all of them as (~0, kNone) (tile_base = the scanned tile counts).
-__global__ __launch_bounds__(256) void ralledata_diff_compact_kernel(const uint8_t* __restrict__ part,
-                                                                     const uint64_t* __restrict__ hash, uint64_t n,
-                                                                     const uint64_t* __restrict__ tile_base,
-                                                                     uint64_t ntiles, uint64_t* __restrict__ keys,
-                                                                     uint32_t* __restrict__ idx) {
-  typedef hipcub::BlockScan<uint32_t, kDiffBlobs> Scan;
-  __shared__ typename Scan::TempStorage tmp;
-  const uint64_t g = (uint64_t)blockIdx.x * kDiffBlobs + threadIdx.x;
-  const uint32_t p = g < n && part[g] ? 1u : 0u;
-  uint32_t rank;
-  Scan(tmp).ExclusiveSum(p, rank);
-  if (g >= n) return;
-  const uint64_t before = tile_base[blockIdx.x] + rank;
-  const uint64_t pos = p ? before : tile_base[ntiles] + (g - before);
-  keys[pos] = p ? hash[g] : ~0ull;
-  idx[pos] = p ? (uint32_t)g : kNone;
-}
-
-// mark[p] = p + 1 for a sorted entry of B, else 0: the max-scan's input.
-__global__ __launch_bounds__(256) void ralledata_diff_mark_kernel(const uint32_t* __restrict__ idx, uint64_t n,
-                                                                  uint64_t nb, uint32_t* __restrict__ mark) {
-  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p < n) mark[p] = idx[p] < nb ? (uint32_t)(p + 1) : 0u;
-}
-
-struct MaxU32 {
-  __host__ __device__ __forceinline__ uint32_t operator()(uint32_t x, uint32_t y) const { return x > y ? x : y; }
-};
-
 struct Lens {
   uint64_t v, s, a;  // val, skey, attrs length
 };
@@ -197,20 +166,7 @@ __global__ __launch_bounds__(kDiffResolveBlock) void ralledata_diff_resolve_kern
   uint32_t r = K2H_AMD_DIFF_PART | ((sa.attrs & kFlagData) ? K2H_AMD_DIFF_DATA : 0u);
 
   // the last blob of B with i's identity: backward over the run's B entries
-  uint32_t j = kNone;
-  Side sb = sa;
-  for (uint64_t q = last_b[p]; q > 0; --q) {
-    const uint64_t hq = keys[q - 1];
-    if ((hq ^ h) & mask) break;
-    if (hq != h) continue;  // another hash with the same sorted bits
-    const uint32_t c = idx[q - 1];
-    if (c >= nb) break;  // (never: in a run every entry before a B entry is B's)
-    const Side sc = side[c];
-    if (sc.sub != sa.sub || sc.klen != sa.klen || !same_key(a.blobs + sa.koff, b.blobs + sc.koff, sa.klen)) continue;
-    j = c;
-    sb = sc;
-    break;
-  }
+  const uint32_t j = last_held(keys, idx, side, last_b[p], h, mask, nb, sa, a.blobs, b.blobs);
 
   // another participant of A with i's stored hash: forward, then backward, over the run's A entries
   bool repeat = false;
@@ -240,7 +196,8 @@ __global__ __launch_bounds__(kDiffResolveBlock) void ralledata_diff_resolve_kern
     work[i] = bytes ? j : kNone;
     if (seen) seen[j] = 1;
     if constexpr (TM) {
-      if (!(sb.attrs & kFlagAttrs) || (sb.attrs & kFlagExpired) || !(sb.attrs & kFlagMtime)) {
+      const uint64_t fb = side[j].attrs;  // the matched blob's flags, read behind the walk (last_held)
+      if (!(fb & kFlagAttrs) || (fb & kFlagExpired) || !(fb & kFlagMtime)) {
         apply = true;  // no attrs page, :390, :395
       } else {
         const DiffMtime mb = tm.mt[j];
@@ -361,20 +318,14 @@ __global__ __launch_bounds__(kDiffBlobs) void ralledata_diff_compare_kernel(Diff
 static_assert(K2H_AMD_DIFF_SKEY == K2H_AMD_DIFF_VAL << 1 && K2H_AMD_DIFF_ATTRS == K2H_AMD_DIFF_VAL << 2,
               "the three differ bits in segment order");
 
-// The call's temporaries: one grow-only buffer per device under a lock with its event, the
-// pattern of the dedup's scratch.  With n = na + nb: two key and two index columns and the side
+// The call's temporaries: one grow-only buffer per device under a lock with its event
+// (RalleScratch, k2h_ralle_ident.h).  With n = na + nb: two key and two index columns and the side
 // records (56 n bytes), a participant byte per blob, the tile counts and their scan, the
 // counters and the library's own storage; with times 16 n more for the mtimes.  The scan column
 // and the work items need none of their own: after the sort its input columns are free, and the
 // mark column takes the index column's place, the scanned positions and the na work items the
 // two halves of the key column's.
-struct DiffScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-};
-DiffScratch g_diff[64];
+RalleScratch g_diff[64];
 
 }  // namespace
 
@@ -399,8 +350,8 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
   const int sort_bits = sort_bits_for(n);
   tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
-  tr(hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, MaxU32(), n,
-                                       stream));
+  tr(hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                       RalleMaxU32(), n, stream));
   if (e != hipSuccess) {
     *herr = e;
     return K2H_AMD_EHIP;
@@ -411,28 +362,9 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
   if (max_bytes > tmp_bytes) tmp_bytes = max_bytes;
   const size_t cm = times ? align256(n * sizeof(DiffMtime)) : 0;
   const size_t total = 2 * c8 + 2 * c4 + cs + cp + 2 * ct + kDiffCounterBytes + align256(tmp_bytes) + cm;
-  DiffScratch& sc = g_diff[dev];
+  RalleScratch& sc = g_diff[dev];
   std::lock_guard<std::mutex> lk(sc.mu);
-  if (!sc.done) tr(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-  if (e == hipSuccess && sc.bytes < total) {
-    if (sc.p) tr(hipFree(sc.p));  // waits for the device: no earlier call's kernel still uses it
-    sc.p = nullptr;
-    sc.bytes = 0;
-    const hipError_t m = e == hipSuccess ? hipMalloc(&sc.p, total) : e;
-    if (m == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      sc.p = nullptr;
-      *herr = m;
-      return K2H_AMD_ENOMEM;
-    }
-    tr(m);
-    if (e == hipSuccess) sc.bytes = total;
-  }
-  if (e == hipSuccess) tr(hipStreamWaitEvent(stream, sc.done, 0));  // never recorded: no wait
-  if (e != hipSuccess) {
-    *herr = e;
-    return K2H_AMD_EHIP;
-  }
+  if (const int rc = sc.reserve(total, stream, herr)) return rc;
   uint8_t* at = (uint8_t*)sc.p;
   auto take = [&](size_t bytes) {
     uint8_t* p = at;
@@ -476,19 +408,19 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
   }
   if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, tile_count, tile_base, nt + 1, stream));
   if (e == hipSuccess) {
-    ralledata_diff_compact_kernel<<<(unsigned)nt, kDiffBlobs, 0, stream>>>(part, keys_out, n, tile_base, nt, keys_in,
-                                                                          idx_in);
+    ralle_compact_kernel<kDiffBlobs><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(part, keys_out, n, tile_base, nt, 0,
+                                                                             keys_in, idx_in);
     tr(hipGetLastError());
   }
   if (e == hipSuccess)
     tr(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint64_t*)keys_in, keys_out,
                                           (const uint32_t*)idx_in, idx_out, n, 0, sort_bits, stream));
   if (e == hipSuccess) {
-    ralledata_diff_mark_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(idx_out, n, nb, mark);
+    ralle_mark_kernel<256><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(idx_out, n, nb, mark);
     tr(hipGetLastError());
   }
   if (e == hipSuccess)
-    tr(hipcub::DeviceScan::InclusiveScan(tmp, max_bytes, (const uint32_t*)mark, last_b, MaxU32(), n, stream));
+    tr(hipcub::DeviceScan::InclusiveScan(tmp, max_bytes, (const uint32_t*)mark, last_b, RalleMaxU32(), n, stream));
   if (e == hipSuccess) {
     const uint64_t grid = (n + kDiffResolveBlock - 1) / kDiffResolveBlock;
     const uint64_t mask = sort_bits == 64 ? ~0ull : (1ull << sort_bits) - 1;

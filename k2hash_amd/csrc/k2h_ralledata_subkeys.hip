@@ -224,8 +224,7 @@ __global__ __launch_bounds__(kSkBlock) void subkeys_resolve_kernel(
         const uint32_t sc = p + 1 < N ? bound_s[N - 2 - p] : 0u;
         q0 = sc ? N - sc : N;
       }
-      Side sb;
-      const uint32_t j = last_held(keys, idx, side, q0, keys[p], mask, n, sa, blobs, blobs, sb);
+      const uint32_t j = last_held(keys, idx, side, q0, keys[p], mask, n, sa, blobs, blobs);
       if (g >= n) {
         child[g - n] = j == kNone ? ~0ull : (uint64_t)j;
         dangling = j == kNone;

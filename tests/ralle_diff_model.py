@@ -1,5 +1,5 @@
-"""Helper for tests/test_ralledata_diff.py and tests/test_ralledata_diff_4gib.py (not a test
-module, not a conftest).
+"""Helper for tests/test_ralledata_diff.py, tests/test_ralledata_diff_held.py and
+tests/test_ralledata_diff_4gib.py (not a test module, not a conftest).
 
 * diff_model: what k2h_amd_ralledata_diff reports (include/k2hash_amd.h section 4b'''''), as a
   sequential pass: a dict from identity -- stored hash, stored subhash, key bytes -- to the last
@@ -8,6 +8,8 @@ module, not a conftest).
 * feed_of / feed_blobs: the mask the header defines from rel, and the replay's two policies.
 * The compare kernel's threshold and the resolve kernel's block width, read from the source.
 * run_diff: the C call into sentinel-filled outputs.
+* assert_diff / explain: the comparison, and what a failure says about a differing blob of A: its
+  attrs kind, the held blobs of its stored hash, and both answers' bits by name.
 """
 import re
 
@@ -158,13 +160,69 @@ def run_diff(cuda, ta, a_size, a_off, tb, b_size, b_off, a_consider=None, b_cons
             seen.cpu().numpy() if want[1] and nb else None, [int(c) for c in counts] if want[2] else None)
 
 
-def assert_diff(got, want, what):
+BIT_NAMES = ((PART, "PART"), (FOUND, "FOUND"), (VAL, "VAL"), (SKEY, "SKEY"), (ATTRS, "ATTRS"), (DATA, "DATA"),
+             (REPEAT, "REPEAT"), (APPLY, "APPLY"))
+
+
+def bits_by_name(r):
+    return "|".join(name for bit, name in BIT_NAMES if int(r) & bit) or "0"
+
+
+def _kind_names():
+    names = {bytes(v): k for k, v in tm.ATTRS_KINDS.items()}
+    for k, table in tm.prior_states(None).items():
+        for _v, _s, attrs in table.values():
+            names.setdefault(bytes(attrs or b""), k)
+    return names
+
+
+def attrs_kind(attrs):
+    """The name of the attrs bytes among tm.ATTRS_KINDS and the tm.prior_states attrs, else "other"."""
+    return _kind_names().get(bytes(attrs), "other")
+
+
+def explain(i, a, b, a_consider=None, b_consider=None, got=None, want=None):
+    """Blob i of A for a failure message: its attrs kind and key length, every participant of B
+    that shares its stored hash, in order, with what of the identity it shares and its attrs
+    kind, and the model's and the device's rel and match (got, want: (rel, match, ...), match may
+    be None)."""
+    (a_buf, a_off), (b_buf, b_off) = a, b
+    mine = [(ident, segs) for k, ident, segs in _participants(a_buf, a_off, None, a_consider) if k == i]
+    if not mine:
+        line = f"A[{i}]: takes no part"
+    else:
+        ident, segs = mine[0]
+        held = [f"B[{j}] sub {'=' if d[1] == ident[1] else '!'} key {'=' if d[2] == ident[2] else '!'} "
+                f"{attrs_kind(s[2])}" for j, d, s in _participants(b_buf, b_off, None, b_consider) if d[0] == ident[0]]
+        line = (f"A[{i}] {attrs_kind(segs[2])}, key of {len(ident[2])} bytes, hash {ident[0]:#x} held by: "
+                + ("; ".join(held) or "none"))
+    for name, res in (("model", want), ("device", got)):
+        if res is not None:
+            m = "-" if res[1] is None else "none" if int(res[1][i]) == NONE else int(res[1][i])
+            line += f"\n    {name}: {bits_by_name(res[0][i])}, match {m}"
+    return line
+
+
+def assert_diff(got, want, what, streams=None, consider=(None, None), shown=4):
+    """streams: (a, b), each (buf, off); with them a failure describes the first `shown`
+    differing blobs of A through explain()."""
     for name, g, w in zip(("rel", "match", "seen"), got[:3], want[:3]):
         if g is None:
             continue
         bad = np.nonzero(g != w)[0]
-        assert bad.size == 0, (f"{what}: {name} differs at {int(bad[0])}: got {int(g[bad[0]]):#x}, "
-                               f"want {int(w[bad[0]]):#x} ({bad.size} in all)")
+        if bad.size == 0:
+            continue
+        told = ""
+        if streams is not None:
+            if name == "seen":   # the blobs of A that the model or the device matched to these blobs of B
+                hit = set(int(j) for j in bad[:shown])
+                pick = [i for i in range(len(want[0])) if int(want[1][i]) in hit
+                        or (got[1] is not None and int(got[1][i]) in hit)][:shown]
+            else:
+                pick = [int(i) for i in bad[:shown]]
+            told = "".join("\n  " + explain(i, *streams, *consider, got=got, want=want) for i in pick)
+        assert False, (f"{what}: {name} differs at {int(bad[0])}: got {int(g[bad[0]]):#x}, "
+                       f"want {int(w[bad[0]]):#x} ({bad.size} in all){told}")
     if got[3] is not None:
         assert got[3] == want[3], f"{what}: counts {got[3]}, want {want[3]}"
 
@@ -178,5 +236,5 @@ def against_model(cuda, a, b, what, shifts=(3, 11), a_consider=None, b_consider=
     ta = tm.place(cuda, a_buf, shifts[0], tail_pad=tail_pad)
     tb = tm.place(cuda, b_buf, shifts[1], canary=0x5A, tail_pad=tail_pad)
     got = run_diff(cuda, ta, len(a_buf), a_off, tb, len(b_buf), b_off, a_consider, b_consider, times, want)
-    assert_diff(got, model, what)
+    assert_diff(got, model, what, (a, b), (a_consider, b_consider))
     return model

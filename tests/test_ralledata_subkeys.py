@@ -207,13 +207,14 @@ def forest(oracle, variant=0, seed=7):
     # keys[31]'s blob stores a wrong hash: not found by name
     dm.set_hash(blobs[31], rm.get(blobs[31], 0, rm.F_HASH) ^ (1 << 50))
     # behind every blob: blobs of other keys whose stored hash agrees with a named target's in the low 40 bits
-    # (every sorted bit), with its subhash, and with both and the key's length -- the resolve steps over them
+    # (every sorted bit), with its subhash, with both and the key's length, and the target's own key under its
+    # hash and another subhash -- the resolve steps over them
     shadows = []
     for t in range(100, 112):
         h, s = rm.get(blobs[t], 0, rm.F_HASH), rm.get(blobs[t], 0, rm.F_SUBHASH)
         other = bytes((x + 1) & 0xff for x in keys[t])
         for j, (key, hh, ss) in enumerate(((b"shadow-a-%d" % t, h ^ (1 << 44), None), (b"shadow-b-%d" % t, h, None),
-                                           (other, h, s))):
+                                           (other, h, s), (keys[t], h, s ^ 1))):
             b = sm.blobs_with_lists(oracle, [key], [sm.serialize([keys[t]]) if j == 0 else b""], variant=variant)[0]
             shadows.append(dm.set_hash(b, hh, ss))
     lists_named = [sm.serialize([keys[t] for t in range(100, 112)])]
@@ -319,6 +320,11 @@ def test_forest_runs_the_step_over_path(oracle):
         if c != NONE:
             stepped += any(i > c and ident != m.ident_of[c] for i, ident in by_low[m.hashes[nm][0] & mask])
     assert stepped >= 5
+    subs = {}                 # a named target's hash and key under two subhashes, the key of more than one chunk
+    for _i, (h, s, key) in m.ident_of.items():
+        subs.setdefault((h, key), set()).add(s)
+    named = {nm for e, nm in enumerate(m.names) if int(m.child[e]) != NONE}
+    assert any(len(v) > 1 and len(key) > 16 and key in named for (_h, key), v in subs.items())
     assert m.counts[2] >= 3 and m.counts[4] >= 20
     per = np.diff(m.edge_off.astype(np.int64))
     assert {0, 1, 2, 63, 64, 65, 300} <= set(int(x) for x in per)

@@ -51,7 +51,7 @@ def fold_stages(path, reps):
             continue
         cur[stage] += dur
         cur["sort_kernels"] += stage == "sort"
-        if "ralledata_dedup_compact_kernel" in name:
+        if "ralle_compact_kernel" in name:
             stage = "sort"
     assert len(calls) >= 2 * reps, f"{len(calls)} dedup calls in the trace, {2 * reps} wanted"
     calls = calls[-2 * reps:]

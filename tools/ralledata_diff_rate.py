@@ -50,7 +50,7 @@ def fold_stages(path, reps):
             cur, stage = dict.fromkeys(STAGES, 0.0), "gather"
         if cur is None:
             continue
-        if "ralledata_diff_mark_kernel" in name:
+        if "ralle_mark_kernel" in name:
             stage = "resolve"
         if "ralledata_diff_compare_kernel" in name:
             cur["compare"] = dur
@@ -58,7 +58,7 @@ def fold_stages(path, reps):
             cur = None
             continue
         cur[stage] += dur
-        if "ralledata_diff_compact_kernel" in name:
+        if "ralle_compact_kernel" in name:
             stage = "sort"
     assert len(calls) >= 2 * reps, f"{len(calls)} diff calls in the trace, {2 * reps} wanted"
     calls = calls[-2 * reps:]
