@@ -711,6 +711,102 @@ int k2h_amd_ralledata_reach(const uint64_t* edge_off, const uint64_t* child, con
                             uint64_t* counts,         /* host, required: blobs reached, levels run, converged (0/1) */
                             void* stream);
 
+/* 4b'''''''. Subkey names unlinked from a stream: the first call that rewrites blobs.  Every
+ * call above keeps or drops whole blobs.  The reference's removal of a subkey,
+ * K2HShm::Remove(key, subkey) with RemoveEx(pElement, bySubKey, ...) (lib/k2hshm.cc:2567-2667),
+ * has two halves: it erases the name from the parent's list (K2HSubKeys::erase), serializes the
+ * list again and replaces the subkeys page; only then does it remove the child with everything
+ * below it.  _reach and _select are the second half; this call is the first, fused with
+ * _select's keep mask, so "remove these subtrees and unlink them" is one pass over the stream.
+ *
+ * blobs, blob_off, keep, sk_flags, edge_off, drop, out, out_off, index and changed are device
+ * pointers; counts is a host pointer.  sk_flags and edge_off are what _subkeys wrote for the same
+ * stream; drop has E = edge_off[n] bytes, drop[e] != 0 leaves the entry of edge e out (NULL:
+ * nothing is dropped, and the call is _select).  k2h_amd_subkeys_drop_mask makes such a mask
+ * from _subkeys' child and a per-blob mask such as _reach's.
+ *
+ * Which blobs are emitted: exactly _select's rule.  Blob i is emitted when keep is NULL or
+ * keep[i] != 0 and its span is valid (non-decreasing, ending at or before size).  Emitted
+ * blobs lie back to back, in order, in out; out_off (n + 1 entries of room) receives the
+ * emitted blobs' offsets plus one, starting at 0; index (may be NULL) their original indices.
+ *
+ * Which emitted blobs are rewritten: those with K2H_AMD_SKEY_PART and without K2H_AMD_SKEY_BAD
+ * in sk_flags[i] and drop[e] != 0 for at least one e in [edge_off[i], edge_off[i+1]).  Every
+ * other emitted blob is copied byte for byte, slack included; with no drop set anywhere the
+ * output bytes, out_off and index equal _select's.
+ *
+ * The rewritten form.  The new list holds the entries of non-zero length whose edge is not
+ * dropped, in segment order, as K2HSubKeys::Serialize(unsigned char**, size_t&) writes a list
+ * (lib/k2hsubkeys.cc:58-111): a u64 count, then per name a u64 length and the bytes.
+ * Zero-length entries are left out (K2HSubKeys::insert refuses them), bytes after the last
+ * counted entry are left out, the count word is the number of entries written, and a list
+ * with no entry left is no segment at all: skey_length = 0.  The blob is written in
+ * GetElementToBinary's layout (lib/k2hshmdirect.cc:59-89): hash and subhash as stored; key,
+ * value and attrs bytes as stored, from wherever their positions put them; key_pos = 80 and the
+ * running sums, written for zero-length segments too; length exactly 80 plus the four lengths.
+ * The same bytes result wherever the segments lay in the input (permuted, overlapping, with
+ * gaps).  A blob left with a key and nothing else (K2H_AMD_UNLINK_KEY_ONLY) leaves no element
+ * when fed (SetElementByBinArray, lib/k2hshmdirect.cc:438), where Remove(key, subkey) on the
+ * table leaves an element with a key and no value.
+ *
+ * The call trusts nothing it can check.  With a drop mask, every emitted blob with PART and
+ * without BAD in sk_flags has its header judged again by the header tests of section 4b and its
+ * segment walked again by the strict rule of section 4b''''''.  It is copied unchanged and counted
+ * in counts[6] when its header is no participant's, when its walk is BAD, when its walk does
+ * not yield exactly edge_off[i+1] - edge_off[i] edges, or when that range is decreasing or ends
+ * behind E -- whether or not a drop byte is set for it.  (A blob without PART, or with BAD, in
+ * sk_flags is copied and not looked into; with drop NULL no blob is.)  Memory rule, as in
+ * _subkeys: no byte of blobs outside [0, size) is read, except within the aligned 16 bytes
+ * that hold a valid byte; nothing outside a blob's own segments is interpreted; all absolute
+ * offsets are 64-bit.
+ *
+ * One departure from the reference.  For a list that is not strictly ascending the reference's
+ * parse (K2HSubKeys::Serialize(const unsigned char*, size_t) through insert) would sort and
+ * deduplicate; its own writer never produces such a list.  Here the order is kept and every
+ * entry is judged by its own drop byte.  Detecting such lists is out of scope.
+ *
+ *   counts   (host, 7 entries, required) blobs emitted; bytes emitted; blobs rewritten; entries
+ *            dropped; lists emptied; blobs left key-only; mismatches
+ *   changed  (n, may be NULL) K2H_AMD_UNLINK_* per INPUT blob, 0 for every blob not rewritten
+ *
+ * Cost: a sizing pass (offsets, keep and flag bytes; with a drop mask the count pass of _subkeys
+ * over again: every participant's header and one walk of its list), two scans of n + 1 entries,
+ * a copy pass of the select copy's shape
+ * and, only when a blob is rewritten, a pass of 8 lanes per rewritten blob that walks its list
+ * once more and copies every run of consecutive kept entries as one range.  `stream` is
+ * synchronised once, to return counts.  out == NULL: count only -- counts and, if given, changed
+ * are filled.  counts[1] > out_cap: K2H_AMD_EINVAL with counts set and nothing written to out.
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ * counts NULL; with n > 0: blobs, blob_off, sk_flags or edge_off NULL; out != NULL with out_off
+ * NULL; n > 2^32 - 2.  n == 0: K2H_AMD_OK, counts zeroed, out_off[0] = 0 when out_off is given,
+ * no other device work.  Temporary device memory, kept per device between calls: 13 bytes per
+ * blob (an 8-byte place, a 4-byte rank, a flag byte) plus the scans' own.
+ *
+ * k2h_amd_subkeys_drop_mask.  One kernel, asynchronous on `stream`:
+ *   drop[e] = child[e] == ~0 ? dangling != 0 : gone != NULL && child[e] < n && gone[child[e]] != 0
+ * child has `edges` entries (as _subkeys wrote it), gone n bytes (may be NULL), drop `edges`
+ * bytes.  edges == 0 does no work.
+ *
+ * Parity: the rewritten list is pinned by tests/golden/ralle_unlink.json, written by the
+ * reference's own K2HSubKeys::erase and Serialize (tests/golden/gen_ralle_unlink.cc);
+ * Remove(key, subkey) is a restatement (tests/ralle_unlink_model.py). */
+#define K2H_AMD_UNLINK_REWRITTEN 0x1u  /* the blob's list was re-serialized              */
+#define K2H_AMD_UNLINK_EMPTIED   0x2u  /* ... and no name was left: skey_length is now 0 */
+#define K2H_AMD_UNLINK_KEY_ONLY  0x4u  /* ... and the blob now has a key and nothing else */
+
+int k2h_amd_ralledata_unlink(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                             const uint8_t* keep,      /* n, or NULL: every blob */
+                             const uint8_t* sk_flags,  /* n,     as _subkeys wrote it */
+                             const uint64_t* edge_off, /* n + 1, as _subkeys wrote it */
+                             const uint8_t* drop,      /* E = edge_off[n] bytes: != 0 leaves edge e's entry out */
+                             void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
+                             uint8_t* changed,         /* n, may be NULL: K2H_AMD_UNLINK_* per INPUT blob, 0 otherwise */
+                             uint64_t* counts,         /* host, 7 entries, required */
+                             void* stream);
+
+int k2h_amd_subkeys_drop_mask(const uint64_t* child, uint64_t edges, const uint8_t* gone, uint64_t n,
+                              int dangling, uint8_t* drop, void* stream);
+
 /* 4c. Blobs straight from scanned records: the middle of a bulk load whose file is already
  * in device memory.  The device scans of section 5 (k2h_amd_import_scan_device,
  * k2h_amd_archive_scan_device and their _scan_prehash_device forms) report every record as

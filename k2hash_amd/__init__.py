@@ -15,6 +15,8 @@ and (2) a batch C ABI backed by hand-written gfx950 HIP kernels (section 2).
              identity (what an incoming stream changes in a held one)
   subkeys    the subkeys segments of a blob stream read there: names as edges between blobs,
              the subtree a set of roots reaches, and the stream with it kept or removed
+  unlink     subkey names taken out of the lists that carry them: the first calls that rewrite
+             blobs (drop_mask, unlink_subkeys, prune_ralledata; also reachable through subkeys)
   archive    k2hash archives scanned and prehashed on the GPU, and transaction logs folded to
              the records that still matter under Load's rule (fold_device, compact_device)
   shard      multi-GPU partitioning and the RCCL gather of hashes
@@ -27,7 +29,8 @@ from .archive import compact_device, fold_device
 from .ralledata import (Diff, HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
                         dedup_ralledata, diff_ralledata, import_file_to_archive, import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
                         ralledata_to_archive, route_ralledata, select_ralledata)
-from .subkeys import Reach, SubkeyEdges, reach_subkeys, subkey_edges, subtree_ralledata
+from .subkeys import (Reach, SubkeyEdges, Unlinked, drop_mask, prune_ralledata, reach_subkeys, subkey_edges,
+                      subtree_ralledata, unlink_subkeys)
 
 __all__ = [
     "k2h_hash", "k2h_second_hash", "k2h_hash_version", "K2HashDynLib", "K2H_HASH_FUNC",
@@ -38,4 +41,5 @@ __all__ = [
     "dedup_ralledata", "partition_ralledata", "ralledata_to_archive", "import_file_to_archive",
     "blob_times", "TimeWindow", "Times", "fold_device", "compact_device", "diff_ralledata", "Diff",
     "subkey_edges", "reach_subkeys", "subtree_ralledata", "SubkeyEdges", "Reach",
+    "drop_mask", "unlink_subkeys", "prune_ralledata", "Unlinked",
 ]

@@ -84,6 +84,7 @@ K2H_AMD_DIFF_PART, K2H_AMD_DIFF_FOUND, K2H_AMD_DIFF_VAL, K2H_AMD_DIFF_SKEY = 0x0
 K2H_AMD_DIFF_ATTRS, K2H_AMD_DIFF_DATA, K2H_AMD_DIFF_REPEAT, K2H_AMD_DIFF_APPLY = 0x10, 0x20, 0x40, 0x80
 
 K2H_AMD_SKEY_PART, K2H_AMD_SKEY_HAS, K2H_AMD_SKEY_BAD = 0x1, 0x2, 0x4
+K2H_AMD_UNLINK_REWRITTEN, K2H_AMD_UNLINK_EMPTIED, K2H_AMD_UNLINK_KEY_ONLY = 0x1, 0x2, 0x4
 
 _twp = ctypes.POINTER(TimeWindowStruct)
 _dtp = ctypes.POINTER(DiffTimes)
@@ -118,6 +119,8 @@ SIGNATURES = {
     "k2h_amd_ralledata_subkeys": (ctypes.c_int, [_p, _u64, _p, _u64, _p, ctypes.c_uint32, _p, _p, _p, _p, _u64, _u64p,
                                                  _p]),
     "k2h_amd_ralledata_reach": (ctypes.c_int, [_p, _p, _p, _u64, _p, _u64, _p, _u64p, _p]),
+    "k2h_amd_ralledata_unlink": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p, _u64, _p, _p, _p, _u64p, _p]),
+    "k2h_amd_subkeys_drop_mask": (ctypes.c_int, [_p, _u64, _p, _u64, ctypes.c_int, _p, _p]),
     "k2h_amd_ralledata_partition": (ctypes.c_int, [_p, _u64, _p, _u64, _prp, _p, _p, _p, _u64, _p, _p, _p, _u64p,
                                                    _u64p, _p]),
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),

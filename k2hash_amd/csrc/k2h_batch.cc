@@ -992,6 +992,48 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_reach(const uint64_
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_reach", e);
 }
 
+// Section 4b''''''': subkey names unlinked from a stream.  Judged on the host like the ones above.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_unlink(
+    const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const uint8_t* keep,
+    const uint8_t* sk_flags, const uint64_t* edge_off, const uint8_t* drop, void* out, uint64_t out_cap,
+    uint64_t* out_off, uint64_t* index, uint8_t* changed, uint64_t* counts, void* stream) {
+  if (!counts) return fail(K2H_AMD_EINVAL, "ralledata_unlink: NULL counts");
+  for (int k = 0; k < 7; ++k) counts[k] = 0;
+  if (n && !blobs) return fail(K2H_AMD_EINVAL, "ralledata_unlink: NULL blobs");
+  if (n && !blob_off) return fail(K2H_AMD_EINVAL, "ralledata_unlink: NULL blob_off");
+  if (n && !sk_flags) return fail(K2H_AMD_EINVAL, "ralledata_unlink: NULL sk_flags");
+  if (n && !edge_off) return fail(K2H_AMD_EINVAL, "ralledata_unlink: NULL edge_off");
+  if (out && !out_off) return fail(K2H_AMD_EINVAL, "ralledata_unlink: out given without out_off");
+  if (n > 0xFFFFFFFEull) return fail(K2H_AMD_EINVAL, "ralledata_unlink: more than 2^32 - 2 blobs (ranks are 32-bit values)");
+  if (n == 0 && !out_off) return K2H_AMD_OK;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  if (n == 0) {  // no blob: out_off[0] = 0
+    e = hipMemsetAsync(out_off, 0, 8, (hipStream_t)stream);
+    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_unlink: hipMemsetAsync", e);
+  }
+  int rc = k2h::launch_ralledata_unlink(blobs, size, blob_off, n, keep, sk_flags, edge_off, drop, out, out_cap, out_off,
+                                        index, changed, counts, (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EINVAL) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "ralledata_unlink: the %llu bytes of the emitted blobs exceed out_cap %llu",
+             (unsigned long long)counts[1], (unsigned long long)out_cap);
+    return fail(rc, msg);
+  }
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_unlink", e);
+}
+
+__attribute__((visibility("default"))) int k2h_amd_subkeys_drop_mask(const uint64_t* child, uint64_t edges,
+                                                                     const uint8_t* gone, uint64_t n, int dangling,
+                                                                     uint8_t* drop, void* stream) {
+  if (edges == 0) return K2H_AMD_OK;
+  if (!child) return fail(K2H_AMD_EINVAL, "subkeys_drop_mask: NULL child");
+  if (!drop) return fail(K2H_AMD_EINVAL, "subkeys_drop_mask: NULL drop");
+  K2H_GATE();
+  hipError_t e = k2h::launch_subkeys_drop_mask(child, edges, gone, n, dangling, drop, (hipStream_t)stream);
+  return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "launch_subkeys_drop_mask", e);
+}
+
 // Section 4b'': the stream split into parts.  Judged on the host like the three above.
 __attribute__((visibility("default"))) int k2h_amd_ralledata_partition(
     const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const k2h_amd_part_rule* rule,

@@ -157,6 +157,17 @@ int launch_ralledata_reach(const uint64_t* edge_off, const uint64_t* child, cons
                            const uint8_t* roots, uint64_t max_levels, uint8_t* reach, uint64_t* counts,
                            hipStream_t stream, hipError_t* herr);
 
+// Subkey names unlinked from a stream (k2h_ralledata_unlink.hip).  _unlink returns a K2H_AMD_*
+// code (the HIP error in *herr), 1 <= n <= 2^32 - 2, and synchronises the stream once;
+// K2H_AMD_EINVAL: out != NULL and counts[1] > out_cap (counts and changed are filled).
+// _drop_mask is asynchronous on the stream.
+int launch_ralledata_unlink(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                            const uint8_t* keep, const uint8_t* sk_flags, const uint64_t* edge_off,
+                            const uint8_t* drop, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
+                            uint8_t* changed, uint64_t* counts, hipStream_t stream, hipError_t* herr);
+hipError_t launch_subkeys_drop_mask(const uint64_t* child, uint64_t edges, const uint8_t* gone, uint64_t n,
+                                    int dangling, uint8_t* drop, hipStream_t stream);
+
 // The mtime and expire of every blob's attrs and the time-window selection
 // (k2h_ralledata_times.hip).  Asynchronous on the stream; n >= 1, window may be NULL.
 hipError_t launch_ralledata_times(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,

@@ -1,6 +1,7 @@
 """Subkeys followed through a RALLEDATA blob stream on the device (include/k2hash_amd.h section
 4b''''''): the names in every blob's subkeys segment as edges to the blobs they address, what a
-set of root blobs reaches over them, and the stream with such a subtree kept or removed.
+set of root blobs reaches over them, the stream with such a subtree kept or removed, and
+(section 4b''''''') the stream with subkey names unlinked from the lists that carry them.
 
 "The table the stream leaves" is taken as: the last participant of an identity wins.  That holds
 for a feed without the mtime attribute or with non-decreasing times; with mtime-bearing blobs
@@ -144,3 +145,9 @@ def subtree_ralledata(blobs, blob_off, roots, *, remove: bool = False, consider=
             if consider is not None:
                 keep.mul_((consider != 0).to(torch.uint8))
     return select_ralledata(blobs, blob_off, keep, out=out, stream=stream)
+
+
+# Section 4b''''''': names unlinked from the lists that carry them.  The wrappers live in unlink.py
+# (they build on the ones above) and are part of this module's interface.
+from .unlink import (UNLINK_EMPTIED, UNLINK_KEY_ONLY, UNLINK_REWRITTEN, UnlinkCounts, Unlinked,  # noqa: E402,F401
+                     drop_mask, prune_ralledata, unlink_subkeys)
