@@ -29,6 +29,7 @@
 #include "../../include/k2hash_amd.h"
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
+#include "k2h_scratch.h"
 
 namespace k2h {
 namespace {
@@ -455,23 +456,25 @@ __global__ __launch_bounds__(kThreads) void arc_emit_kernel(FileView fv, const u
 
 unsigned blocks_for(uint64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-// The scan's temporaries, as the import scanner keeps them (ScanScratch, k2h_import_dev.hip):
-// one grow-only buffer per device, held across calls under a per-device lock while it stays
-// within kScratchKeep and freed at the end of a call that needed more.  Per candidate: its
-// offset and its record's next offset (16 B), next and the two jump arrays (12 B), reach and
-// rank (8 B); per 4 KiB wave of
+// The scan's temporaries (k2h_scratch.h), as the import scanner keeps them: freed at the end of
+// a call that needed more than kScratchKeep, and neither an event nor a wait, since the call
+// synchronises its stream before it unlocks.  Per candidate: its offset and its record's next
+// offset (16 B), next and the two jump arrays (12 B), reach and rank (8 B); per 4 KiB wave of
 // the file 16 B of counts.  The record count comes back through mapped pinned host memory.
-constexpr uint64_t kScratchKeep = 512ull << 20;
-struct ArcScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
+struct ArcState {
+  DeviceScratch buf;
   uint64_t* hflags = nullptr;    // mapped pinned host memory: [0] record count, [1] candidates
   uint64_t* hflags_d = nullptr;  // ... and its device address
 };
-ArcScratch g_arc[64];
+PerDevice<ArcState> g_arc;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct ArcCols {
+  uint64_t *wcnt, *woff;
+  void* tmp;
+  uint64_t *cand, *nxtoff;
+  uint32_t *next, *ja, *jb, *reach, *rank;
+  size_t total;
+};
 
 }  // namespace
 
@@ -485,28 +488,23 @@ int launch_archive_scan(const void* file, uint64_t size, k2h_amd_archive_rec* re
   const uint64_t nwave = (size + kDetWave - 1) / kDetWave;
   const uint64_t nblk = (nwave + kDetWavesPerBlock - 1) / kDetWavesPerBlock;
   if (nblk > 0x7FFFFFFFull) return K2H_AMD_EINVAL;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
-  if (e != hipSuccess) {
-    *herr = e;
+  FirstError tr;
+  ArcState* const scp = g_arc.current(tr);
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
   // the chain has at most size / 104 records; 2^rounds hops cover it
   uint32_t rounds = 0;
   while ((size / kScom) >> rounds) ++rounds;
-  ArcScratch& sc = g_arc[dev];
-  std::lock_guard<std::mutex> lk(sc.mu);
+  ArcState& sc = *scp;
+  std::lock_guard<std::mutex> lk(sc.buf.mu);
   if (!sc.hflags) {
     void* hp = nullptr;
     tr(hipHostMalloc(&hp, 64, hipHostMallocMapped));
     void* dp = nullptr;
-    if (e == hipSuccess) tr(hipHostGetDevicePointer(&dp, hp, 0));
-    if (e == hipSuccess) {
+    if (tr.ok()) tr(hipHostGetDevicePointer(&dp, hp, 0));
+    if (tr.ok()) {
       sc.hflags = (uint64_t*)hp;
       sc.hflags_d = (uint64_t*)dp;
     } else if (hp) {
@@ -521,78 +519,72 @@ int launch_archive_scan(const void* file, uint64_t size, k2h_amd_archive_rec* re
   uint64_t ccap = size / kScom + 1;
   uint64_t nrec = 0;
   int rc = K2H_AMD_OK;
-  for (int attempt = 0; attempt < 2 && e == hipSuccess; ++attempt) {
+  for (int attempt = 0; attempt < 2 && tr.ok(); ++attempt) {
     size_t tmp1 = 0, tmp2 = 0;
     tr(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (uint64_t*)nullptr, (uint64_t*)nullptr, nwave + 1, stream));
     tr(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (uint32_t*)nullptr, (uint32_t*)nullptr, ccap + 1, stream));
-    if (e != hipSuccess) break;
-    const size_t o_wcnt = 0, o_woff = o_wcnt + align256((nwave + 1) * 8), o_tmp = o_woff + align256((nwave + 1) * 8);
-    const size_t o_cand = o_tmp + align256(tmp1 > tmp2 ? tmp1 : tmp2), o_nxo = o_cand + align256(ccap * 8);
-    const size_t o_next = o_nxo + align256(ccap * 8);
-    const size_t o_ja = o_next + align256(ccap * 4), o_jb = o_ja + align256(ccap * 4);
-    const size_t o_reach = o_jb + align256(ccap * 4), o_rank = o_reach + align256((ccap + 1) * 4);
-    const size_t total = o_rank + align256((ccap + 1) * 4);
-    if (sc.bytes < total) {
-      if (sc.p) tr(hipFree(sc.p));
-      sc.p = nullptr;
-      sc.bytes = 0;
-      const hipError_t a = e == hipSuccess ? hipMalloc(&sc.p, total) : e;
-      if (a == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        sc.p = nullptr;
-        rc = K2H_AMD_ENOMEM;
-        break;
-      }
-      tr(a);
-      if (e == hipSuccess) sc.bytes = total;
+    if (!tr.ok()) break;
+    auto layout = [&](void* base) {
+      Carver c(base);
+      ArcCols k;
+      k.wcnt = c.take<uint64_t>(nwave + 1);
+      k.woff = c.take<uint64_t>(nwave + 1);
+      k.tmp = c.bytes(tmp1 > tmp2 ? tmp1 : tmp2);
+      k.cand = c.take<uint64_t>(ccap);
+      k.nxtoff = c.take<uint64_t>(ccap);
+      k.next = c.take<uint32_t>(ccap);
+      k.ja = c.take<uint32_t>(ccap);
+      k.jb = c.take<uint32_t>(ccap);
+      k.reach = c.take<uint32_t>(ccap + 1);
+      k.rank = c.take<uint32_t>(ccap + 1);
+      k.total = c.total();
+      return k;
+    };
+    hipError_t ge = hipSuccess;
+    if (sc.buf.grow(layout(nullptr).total, &ge) == K2H_AMD_ENOMEM) {
+      rc = K2H_AMD_ENOMEM;
+      break;
     }
-    if (e != hipSuccess) break;
+    tr(ge);
+    if (!tr.ok()) break;
     sc.hflags[0] = 0;  // the previous call on this device has synchronised (the lock)
     sc.hflags[1] = 0;
-    uint8_t* base = (uint8_t*)sc.p;
-    uint64_t* wcnt = (uint64_t*)(base + o_wcnt);
-    uint64_t* woff = (uint64_t*)(base + o_woff);
-    void* tmp = base + o_tmp;
-    uint64_t* cand = (uint64_t*)(base + o_cand);
-    uint64_t* nxtoff = (uint64_t*)(base + o_nxo);
-    uint32_t* next = (uint32_t*)(base + o_next);
-    uint32_t* jbuf[2] = {(uint32_t*)(base + o_ja), (uint32_t*)(base + o_jb)};
-    uint32_t* reach = (uint32_t*)(base + o_reach);
-    uint32_t* rank = (uint32_t*)(base + o_rank);
+    const ArcCols k = layout(sc.buf.p);
+    uint32_t* jbuf[2] = {k.ja, k.jb};
     const unsigned gc = blocks_for(ccap);
-    tr(hipMemsetAsync(wcnt + nwave, 0, 8, stream));
-    tr(hipMemsetAsync(reach, 0, (ccap + 1) * 4, stream));
-    if (e == hipSuccess) {
-      arc_count_kernel<<<(unsigned)nblk, kThreads, 0, stream>>>(fv, nwave, wcnt);
+    tr(hipMemsetAsync(k.wcnt + nwave, 0, 8, stream));
+    tr(hipMemsetAsync(k.reach, 0, (ccap + 1) * 4, stream));
+    if (tr.ok()) {
+      arc_count_kernel<<<(unsigned)nblk, kThreads, 0, stream>>>(fv, nwave, k.wcnt);
       tr(hipGetLastError());
     }
-    if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, tmp1, wcnt, woff, nwave + 1, stream));
-    if (e == hipSuccess) {
-      arc_write_kernel<<<(unsigned)nblk, kThreads, 0, stream>>>(fv, nwave, woff, ccap, cand, nxtoff, sc.hflags_d);
+    if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tmp1, k.wcnt, k.woff, nwave + 1, stream));
+    if (tr.ok()) {
+      arc_write_kernel<<<(unsigned)nblk, kThreads, 0, stream>>>(fv, nwave, k.woff, ccap, k.cand, k.nxtoff, sc.hflags_d);
       tr(hipGetLastError());
     }
-    if (e == hipSuccess) {
-      arc_link_kernel<<<gc, kThreads, 0, stream>>>(woff, nwave, ccap, cand, nxtoff, next, reach);
+    if (tr.ok()) {
+      arc_link_kernel<<<gc, kThreads, 0, stream>>>(k.woff, nwave, ccap, k.cand, k.nxtoff, k.next, k.reach);
       tr(hipGetLastError());
     }
-    const uint32_t* jin = next;
-    for (uint32_t r = 0; r < rounds && e == hipSuccess; ++r) {
-      arc_jump_kernel<<<gc, kThreads, 0, stream>>>(woff, nwave, ccap, jin, jbuf[r & 1], reach);
+    const uint32_t* jin = k.next;
+    for (uint32_t r = 0; r < rounds && tr.ok(); ++r) {
+      arc_jump_kernel<<<gc, kThreads, 0, stream>>>(k.woff, nwave, ccap, jin, jbuf[r & 1], k.reach);
       tr(hipGetLastError());
       jin = jbuf[r & 1];
     }
-    if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, tmp2, reach, rank, ccap + 1, stream));
-    if (e == hipSuccess) {
+    if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tmp2, k.reach, k.rank, ccap + 1, stream));
+    if (tr.ok()) {
       if (hash)
-        arc_emit_kernel<true><<<gc, kThreads, 0, stream>>>(fv, woff, nwave, ccap, cand, next, reach, rank, recs, cap,
-                                                           sp, ho, sc.hflags_d);
+        arc_emit_kernel<true><<<gc, kThreads, 0, stream>>>(fv, k.woff, nwave, ccap, k.cand, k.next, k.reach, k.rank,
+                                                           recs, cap, sp, ho, sc.hflags_d);
       else
-        arc_emit_kernel<false><<<gc, kThreads, 0, stream>>>(fv, woff, nwave, ccap, cand, next, reach, rank, recs, cap,
-                                                            sp, ho, sc.hflags_d);
+        arc_emit_kernel<false><<<gc, kThreads, 0, stream>>>(fv, k.woff, nwave, ccap, k.cand, k.next, k.reach, k.rank,
+                                                            recs, cap, sp, ho, sc.hflags_d);
       tr(hipGetLastError());
     }
     tr(hipStreamSynchronize(stream));
-    if (e != hipSuccess) break;
+    if (!tr.ok()) break;
     const uint64_t ncand = __atomic_load_n(&sc.hflags[1], __ATOMIC_ACQUIRE);
     if (ncand <= ccap) {
       nrec = __atomic_load_n(&sc.hflags[0], __ATOMIC_ACQUIRE);
@@ -604,13 +596,9 @@ int launch_archive_scan(const void* file, uint64_t size, k2h_amd_archive_rec* re
     }
     ccap = ncand;
   }
-  if (sc.bytes > kScratchKeep) {  // the stream is synchronised: no kernel still reads it
-    (void)hipFree(sc.p);
-    sc.p = nullptr;
-    sc.bytes = 0;
-  }
-  *herr = e;
-  if (e != hipSuccess) return e == hipErrorOutOfMemory ? K2H_AMD_ENOMEM : K2H_AMD_EHIP;
+  sc.buf.release_above(kScratchKeep);
+  *herr = tr.e;
+  if (!tr.ok()) return tr.e == hipErrorOutOfMemory ? K2H_AMD_ENOMEM : K2H_AMD_EHIP;
   if (rc != K2H_AMD_OK) return rc;
   *count = nrec;
   return (recs && nrec > cap) ? K2H_AMD_EINVAL : K2H_AMD_OK;

@@ -54,6 +54,7 @@
 
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
+#include "k2h_scratch.h"
 
 // Dynamic LDS, never touched, that a build can give to the link and cover kernels so that fewer
 // blocks fit a CU: 64 KiB leaves two 256-thread blocks per CU, two waves per SIMD; 0 leaves
@@ -71,7 +72,6 @@ namespace {
 
 constexpr int kFoldRecs = 256;           // every kernel: records (or sorted positions) per block, one per thread
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // no record: a pair's index, a summary's nxt
-constexpr int kCounters = 64;            // finish counts into this many words, each on a 64-byte line of its own
 constexpr int kMaxRounds = 32;           // nxt points to a later record, n < 2^32: a chain has fewer than 2^32 links
 constexpr size_t kLinkLds = K2H_FOLD_LINK_LDS, kCoverLds = K2H_FOLD_COVER_LDS;
 
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(kFoldRecs) void archive_fold_cover_kernel(const uin
   if (__ballot(open) && (threadIdx.x & 63u) == 0) *flag = 1u;
 }
 
-// keep[i] = 0 for the covered records; their number into the kCounters words of `dropped`.
+// keep[i] = 0 for the covered records; their number into word 0 of the counter lines of `dropped`.
 __global__ __launch_bounds__(kFoldRecs) void archive_fold_finish_kernel(const uint64_t* __restrict__ sum, uint64_t n,
                                                                        uint8_t* __restrict__ keep,
                                                                        unsigned long long* __restrict__ dropped) {
@@ -256,37 +256,28 @@ __global__ __launch_bounds__(kFoldRecs) void archive_fold_finish_kernel(const ui
   const unsigned long long m = __ballot(drop);
   if ((threadIdx.x & 63u) == 0 && m) {
     const uint32_t wave = blockIdx.x * (kFoldRecs / 64) + (threadIdx.x >> 6);
-    atomicAdd(dropped + 8 * (wave % kCounters), (unsigned long long)__popcll(m));
+    atomicAdd(dropped + 8 * (wave % kCounterLines), (unsigned long long)__popcll(m));
   }
 }
 
-// The call's temporaries: one grow-only buffer per device, held across calls under a
-// per-device lock, with an event the next call's stream waits for (the pattern of
-// RalleScratch, k2h_ralle_ident.h) -- 72 bytes per record (two key and two index
-// columns, the side records, two summary columns), the tile counts and their scan, the round
-// flags, the counters, and the library's own storage.
-struct FoldScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-};
-FoldScratch g_fold[64];
+// The call's temporaries (k2h_scratch.h) -- 72 bytes per record (two key and two index columns,
+// the side records, two summary columns), the tile counts and their scan, the round flags, the
+// counters, and the library's own storage.
+PerDevice<> g_fold;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// The low hash bits the pairs are sorted by, as k2h_ralledata_dedup.hip chooses them: 8 more
-// than the records' number has, in whole bytes, at least 16.  Equal hashes are neighbours
-// under any number of bits; with 8 spare bits about one pair of neighbours in 256 shares the
-// sorted bits without sharing the hash, and the walk steps over those.
-int sort_bits_for(uint64_t n) {
-  int bits = 0;
-  while (bits < 64 && (n - 1) >> bits) ++bits;
-  bits = (bits + 8 + 7) / 8 * 8;
-  return bits < 16 ? 16 : bits > 64 ? 64 : bits;
-}
-constexpr size_t kCounterBytes = 64 * kCounters;
 constexpr size_t kFlagBytes = 256;  // kMaxRounds + 1 words
+
+struct FoldCols {
+  uint64_t *keys_in, *keys_out;  // keys_out: first the records' own hashes (h1 == NULL), then the sorted keys
+  uint64_t *sum_a, *sum_b;
+  uint32_t *idx_in, *idx_out;
+  Side* side;
+  uint64_t *tile_count, *tile_base;
+  uint32_t* flags;
+  unsigned long long* counter;  // right behind the flags: one memset clears both
+  void* tmp;
+  size_t total;
+};
 
 }  // namespace
 
@@ -296,120 +287,96 @@ int launch_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_r
                         hipStream_t stream, hipError_t* herr) {
   *herr = hipSuccess;
   const uint64_t nt = (n + kFoldRecs - 1) / kFoldRecs;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  FirstError tr;
+  DeviceScratch* const sc = g_fold.current(tr);
   size_t scan_bytes = 0, sort_bytes = 0;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
   const int sort_bits = sort_bits_for(n);
   tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
-  if (e != hipSuccess) {
-    *herr = e;
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
-  const size_t c8 = align256(n * 8), c4 = align256(n * 4), cs = align256(n * sizeof(Side)), ct = align256((nt + 1) * 8);
-  const size_t tmp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-  const size_t total = 4 * c8 + 2 * c4 + cs + 2 * ct + kFlagBytes + kCounterBytes + align256(tmp_bytes);
-  FoldScratch& sc = g_fold[dev];
-  std::lock_guard<std::mutex> lk(sc.mu);
-  if (!sc.done) tr(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-  if (e == hipSuccess && sc.bytes < total) {
-    if (sc.p) tr(hipFree(sc.p));  // waits for the device: no earlier call's kernel still uses it
-    sc.p = nullptr;
-    sc.bytes = 0;
-    const hipError_t a = e == hipSuccess ? hipMalloc(&sc.p, total) : e;
-    if (a == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      sc.p = nullptr;
-      *herr = a;
-      return K2H_AMD_ENOMEM;
-    }
-    tr(a);
-    if (e == hipSuccess) sc.bytes = total;
-  }
-  if (e == hipSuccess) tr(hipStreamWaitEvent(stream, sc.done, 0));  // never recorded: no wait
-  if (e != hipSuccess) {
-    *herr = e;
-    return K2H_AMD_EHIP;
-  }
-  uint8_t* base = (uint8_t*)sc.p;
-  uint64_t* keys_in = (uint64_t*)base;
-  uint64_t* keys_out = (uint64_t*)(base + c8);  // first the records' own hashes (h1 == NULL), then the sorted keys
-  uint64_t* sum_a = (uint64_t*)(base + 2 * c8);
-  uint64_t* sum_b = (uint64_t*)(base + 3 * c8);
-  uint32_t* idx_in = (uint32_t*)(base + 4 * c8);
-  uint32_t* idx_out = (uint32_t*)(base + 4 * c8 + c4);
-  Side* side = (Side*)(base + 4 * c8 + 2 * c4);
-  uint64_t* tile_count = (uint64_t*)(base + 4 * c8 + 2 * c4 + cs);
-  uint64_t* tile_base = (uint64_t*)(base + 4 * c8 + 2 * c4 + cs + ct);
-  uint32_t* flags = (uint32_t*)(base + 4 * c8 + 2 * c4 + cs + 2 * ct);
-  unsigned long long* counter = (unsigned long long*)(base + 4 * c8 + 2 * c4 + cs + 2 * ct + kFlagBytes);
-  void* tmp = base + 4 * c8 + 2 * c4 + cs + 2 * ct + kFlagBytes + kCounterBytes;
+  auto layout = [&](void* base) {
+    Carver c(base);
+    FoldCols k;
+    k.keys_in = c.take<uint64_t>(n);
+    k.keys_out = c.take<uint64_t>(n);
+    k.sum_a = c.take<uint64_t>(n);
+    k.sum_b = c.take<uint64_t>(n);
+    k.idx_in = c.take<uint32_t>(n);
+    k.idx_out = c.take<uint32_t>(n);
+    k.side = c.take<Side>(n);
+    k.tile_count = c.take<uint64_t>(nt + 1);
+    k.tile_base = c.take<uint64_t>(nt + 1);
+    k.flags = (uint32_t*)c.bytes(kFlagBytes);
+    k.counter = (unsigned long long*)c.bytes(kCounterBytes);
+    k.tmp = c.bytes(scan_bytes > sort_bytes ? scan_bytes : sort_bytes);
+    k.total = c.total();
+    return k;
+  };
+  std::lock_guard<std::mutex> lk(sc->mu);
+  if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
+  const FoldCols k = layout(sc->p);
   const unsigned grid = (unsigned)nt;
   // entry nt of the counts is 0, so entry nt of their exclusive scan is the totals
-  tr(hipMemsetAsync(tile_count + nt, 0, 8, stream));
-  tr(hipMemsetAsync(flags, 0, kFlagBytes + kCounterBytes, stream));
-  if (e == hipSuccess && !h1) {
+  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  tr(hipMemsetAsync(k.flags, 0, kFlagBytes + kCounterBytes, stream));
+  if (tr.ok() && !h1) {
     ArchiveHashOut ho;
-    ho.h1 = keys_out;
+    ho.h1 = k.keys_out;
     tr(launch_archive_prehash(file, size, recs, n, seed, ho, stream));
   }
-  if (e == hipSuccess) {
-    archive_fold_gather_kernel<<<grid, kFoldRecs, 0, stream>>>(recs, size, n, keep, by, side, sum_a, tile_count);
+  if (tr.ok()) {
+    archive_fold_gather_kernel<<<grid, kFoldRecs, 0, stream>>>(recs, size, n, keep, by, k.side, k.sum_a, k.tile_count);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, tile_count, tile_base, nt + 1, stream));
-  if (e == hipSuccess) {
-    archive_fold_compact_kernel<<<grid, kFoldRecs, 0, stream>>>(keep, h1 ? h1 : keys_out, n, tile_base, nt, side,
-                                                               keys_in, idx_in);
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, scan_bytes, k.tile_count, k.tile_base, nt + 1, stream));
+  if (tr.ok()) {
+    archive_fold_compact_kernel<<<grid, kFoldRecs, 0, stream>>>(keep, h1 ? h1 : k.keys_out, n, k.tile_base, nt, k.side,
+                                                               k.keys_in, k.idx_in);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess)
-    tr(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint64_t*)keys_in, keys_out,
-                                          (const uint32_t*)idx_in, idx_out, n, 0, sort_bits, stream));
-  if (e == hipSuccess) {
-    const uint64_t mask = sort_bits == 64 ? ~0ull : (1ull << sort_bits) - 1;
-    archive_fold_link_kernel<<<grid, kFoldRecs, kLinkLds, stream>>>((const uint8_t*)file, keys_out, idx_out, n, mask,
-                                                                    side, by, sum_a, flags);
+  if (tr.ok())
+    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
+                                          (const uint32_t*)k.idx_in, k.idx_out, n, 0, sort_bits, stream));
+  if (tr.ok()) {
+    const uint64_t mask = sort_mask(sort_bits);
+    archive_fold_link_kernel<<<grid, kFoldRecs, kLinkLds, stream>>>((const uint8_t*)file, k.keys_out, k.idx_out, n,
+                                                                    mask, k.side, by, k.sum_a, k.flags);
     tr(hipGetLastError());
   }
   // the rounds: flags[r] says whether the kernel before round r left a lane unfinished
-  uint64_t *cur = sum_a, *other = sum_b;
-  for (int r = 0; e == hipSuccess; ++r) {
+  uint64_t *cur = k.sum_a, *other = k.sum_b;
+  for (int r = 0; tr.ok(); ++r) {
     uint32_t open = 0;
-    tr(hipMemcpyAsync(&open, flags + r, 4, hipMemcpyDeviceToHost, stream));
+    tr(hipMemcpyAsync(&open, k.flags + r, 4, hipMemcpyDeviceToHost, stream));
     tr(hipStreamSynchronize(stream));
-    if (e != hipSuccess || !open) break;
+    if (!tr.ok() || !open) break;
     if (r == kMaxRounds) {  // (cannot happen: every nxt is a later record)
-      e = hipErrorUnknown;
+      tr.e = hipErrorUnknown;
       break;
     }
-    archive_fold_cover_kernel<<<grid, kFoldRecs, kCoverLds, stream>>>(cur, other, n, flags + r + 1);
+    archive_fold_cover_kernel<<<grid, kFoldRecs, kCoverLds, stream>>>(cur, other, n, k.flags + r + 1);
     tr(hipGetLastError());
     uint64_t* t = cur;
     cur = other;
     other = t;
   }
-  if (e == hipSuccess) {
-    archive_fold_finish_kernel<<<grid, kFoldRecs, 0, stream>>>(cur, n, keep, counter);
+  if (tr.ok()) {
+    archive_fold_finish_kernel<<<grid, kFoldRecs, 0, stream>>>(cur, n, keep, k.counter);
     tr(hipGetLastError());
   }
-  unsigned long long counts[8 * kCounters];
-  if (e == hipSuccess && dropped) tr(hipMemcpyAsync(counts, counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
-  if (e == hipSuccess && dropped) {
+  unsigned long long counts[kCounterBytes / 8];
+  if (tr.ok() && dropped) tr(hipMemcpyAsync(counts, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(sc->mark_done(stream));
+  if (tr.ok() && dropped) {
     tr(hipStreamSynchronize(stream));
-    uint64_t sum = 0;
-    for (int c = 0; c < kCounters; ++c) sum += counts[8 * c];
-    if (e == hipSuccess) *dropped = sum;
+    if (tr.ok()) *dropped = counter_sum(counts, 0);
   }
-  *herr = e;
-  return e != hipSuccess ? K2H_AMD_EHIP : K2H_AMD_OK;
+  *herr = tr.e;
+  return !tr.ok() ? K2H_AMD_EHIP : K2H_AMD_OK;
 }
 
 }  // namespace k2h

@@ -24,6 +24,7 @@
 #include "../../include/k2hash_amd.h"
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
+#include "k2h_scratch.h"
 
 namespace k2h {
 namespace {
@@ -1230,27 +1231,26 @@ __global__ __launch_bounds__(64) void tsv_b_kernel(const uint8_t* __restrict__ f
 
 }  // namespace
 
-// The scan's temporaries, one grow-only buffer per device held across calls (under a
-// per-device lock for the call) while it stays within kScratchKeep: per-call pool
-// allocations of this size cost ~0.15 ms per hipFreeAsync on MI355X (rocprofv3
-// --runtime-trace, profiles/r03f_import_api_stats.csv), more than the scan itself.  Above
-// kScratchKeep (a file of several GB) the buffer is freed at the end of the call, so a huge
-// file does not pin its peak for the life of the process.
+// The scan's temporaries (k2h_scratch.h), freed at the end of a call that needed more than
+// kScratchKeep.  The call synchronises its stream before it unlocks, so it neither leaves an
+// event nor waits for one.
 // The entry-state scan's counter lives in a second buffer that is never freed: it must be
 // zero at every call (the scan leaves it zero), so it is cleared only when allocated.
 // The record count and the mdbm flags come back through mapped pinned host memory.
-constexpr uint64_t kScratchKeep = 512ull << 20;  // > the temporaries of a 1.2 GB TSV file (~20 % of its size)
-struct ScanScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
+struct ScanState {
+  DeviceScratch buf;
   void* cnt = nullptr;      // done (u32) at 0, count (u64) at 8
   uint64_t* hflags = nullptr;    // mapped pinned host memory: [0] count, [1] mdbm header ok, [2] mdbm fixup
   uint64_t* hflags_d = nullptr;  // ... and its device address
 };
-ScanScratch g_scan[64];
+PerDevice<ScanState> g_scan;
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct ScanCols {
+  GFn *blk_fn, *intile, *tile_fn;
+  TState* tile_in;
+  uint64_t *ev, *spec;
+  size_t total;
+};
 
 // TSV and mdbm: pass A, the scan of block functions (and the count), pass B (mdbm always:
 // it checks the header; TSV when records are wanted), one synchronisation.  Temporaries per
@@ -1261,64 +1261,63 @@ template <bool MDBM>
 static int launch_scan(const uint8_t* f, uint64_t size, k2h_amd_import_rec* recs, uint64_t cap, uint64_t* count,
                        hipStream_t stream, hipError_t* herr, uint64_t* h1, uint64_t* h2, uint64_t seed) {
   const uint64_t nblk = (size + kTChunk - 1) / kTChunk;
-  hipError_t e = nblk > 0x7FFFFFFFull ? hipErrorInvalidValue : hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
-  if (e != hipSuccess) {
-    *herr = e;
+  FirstError tr;
+  if (nblk > 0x7FFFFFFFull) tr.e = hipErrorInvalidValue;
+  ScanState* const scp = g_scan.current(tr);
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
   const uint64_t nunit = (size + kUnit - 1) / kUnit;  // pass B's waves and the scan's items
   const uint64_t ntile = (nblk + kTile - 1) / kTile;  // tiles of pass-A blocks
   const size_t nfn = nblk * kUnitsPerBlock;  // pass A writes every wave's function, past-EOF ones too
-  const size_t o_fn = 0, o_in = o_fn + align256(nfn * sizeof(GFn)), o_tf = o_in + align256(nfn * sizeof(GFn));
-  const size_t o_ti = o_tf + align256(ntile * sizeof(GFn)), o_ev = o_ti + align256(ntile * sizeof(TState));
   const size_t nspec = MDBM ? 0 : nblk * kUnitsPerBlock * kUnitSlots;
-  const size_t o_spec = o_ev + align256(nblk * kTThreads * 8);
-  const size_t total = o_spec + align256(nspec * 8);
-  ScanScratch& sc = g_scan[dev];
-  std::lock_guard<std::mutex> lk(sc.mu);
-  if (e == hipSuccess && sc.bytes < total) {
-    if (sc.p) tr(hipFree(sc.p));
-    sc.p = nullptr;
-    sc.bytes = 0;
-    tr(hipMalloc(&sc.p, total));
-    if (e == hipSuccess) sc.bytes = total;
-  }
-  if (e == hipSuccess && !sc.cnt) {
+  auto layout = [&](void* base) {
+    Carver c(base);
+    ScanCols k;
+    k.blk_fn = c.take<GFn>(nfn);
+    k.intile = c.take<GFn>(nfn);
+    k.tile_fn = c.take<GFn>(ntile);
+    k.tile_in = c.take<TState>(ntile);
+    k.ev = c.take<uint64_t>(nblk * kTThreads);
+    k.spec = c.take<uint64_t>(nspec);
+    k.total = c.total();
+    return k;
+  };
+  ScanState& sc = *scp;
+  std::lock_guard<std::mutex> lk(sc.buf.mu);
+  // an allocation that fails is a HIP error of this call like any other (k2h_batch.cc words it)
+  if (sc.buf.grow(layout(nullptr).total, herr) != K2H_AMD_OK) return K2H_AMD_EHIP;
+  if (tr.ok() && !sc.cnt) {
     tr(hipMalloc(&sc.cnt, 256));
     tr(hipMemsetAsync(sc.cnt, 0, 256, stream));
-    if (e != hipSuccess) sc.cnt = nullptr;
+    if (!tr.ok()) sc.cnt = nullptr;
   }
-  if (e == hipSuccess && !sc.hflags) {  // the count and flags come back without a copy command
+  if (tr.ok() && !sc.hflags) {  // the count and flags come back without a copy command
     void* hp = nullptr;
     tr(hipHostMalloc(&hp, 64, hipHostMallocMapped));
     void* dp = nullptr;
-    if (e == hipSuccess) tr(hipHostGetDevicePointer(&dp, hp, 0));
-    if (e == hipSuccess) {
+    if (tr.ok()) tr(hipHostGetDevicePointer(&dp, hp, 0));
+    if (tr.ok()) {
       sc.hflags = (uint64_t*)hp;
       sc.hflags_d = (uint64_t*)dp;
     } else if (hp) {
       (void)hipHostFree(hp);
     }
   }
-  if (e != hipSuccess) {
-    *herr = e;
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
   sc.hflags[1] = 0;  // the previous call on this device has synchronised (the lock)
   sc.hflags[2] = 0;
-  uint8_t* base = (uint8_t*)sc.p;
+  const ScanCols k = layout(sc.buf.p);
   uint8_t* cb = (uint8_t*)sc.cnt;
   EntryScan es;
-  es.blk_fn = (GFn*)(base + o_fn);
-  es.intile = (GFn*)(base + o_in);
-  es.tile_fn = (GFn*)(base + o_tf);
-  es.tile_in = (TState*)(base + o_ti);
+  es.blk_fn = k.blk_fn;
+  es.intile = k.intile;
+  es.tile_fn = k.tile_fn;
+  es.tile_in = k.tile_in;
   es.done = (uint32_t*)cb;
   es.count = (uint64_t*)(cb + 8);
   es.host_count = sc.hflags_d;
@@ -1327,18 +1326,18 @@ static int launch_scan(const uint8_t* f, uint64_t size, k2h_amd_import_rec* recs
   es.size = size;
   es.mdbm = MDBM ? 1u : 0u;
   uint64_t* dcount = es.count;
-  uint64_t* ev = (uint64_t*)(base + o_ev);
-  const SpecSlots spec{(uint64_t*)(base + o_spec)};
+  uint64_t* ev = k.ev;
+  const SpecSlots spec{k.spec};
   const bool walk = MDBM || (recs && cap);
   const uint64_t wcap = recs ? cap : 0;
   const SpadTable sp = make_spad(seed);
   tsv_a_kernel<MDBM><<<(unsigned)nblk, kTThreads, 0, stream>>>(f, size, es.blk_fn, ev, spec, sp);
   tr(hipGetLastError());
-  if (e == hipSuccess) {
+  if (tr.ok()) {
     tsv_scan_kernel<<<(unsigned)ntile, kTThreads, 0, stream>>>(es);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess && walk) {
+  if (tr.ok() && walk) {
     if (h1 && recs)
       tsv_b_kernel<true, MDBM><<<(unsigned)nunit, 64, 0, stream>>>(
           f, size, es.intile, es.tile_in, ev, spec.raw, dcount, wcap, recs, sp, h1, h2, sc.hflags_d);
@@ -1349,22 +1348,18 @@ static int launch_scan(const uint8_t* f, uint64_t size, k2h_amd_import_rec* recs
     tr(hipGetLastError());
   }
   tr(hipStreamSynchronize(stream));
-  const uint64_t n = e == hipSuccess ? __atomic_load_n(&sc.hflags[0], __ATOMIC_ACQUIRE) : 0;
+  const uint64_t n = tr.ok() ? __atomic_load_n(&sc.hflags[0], __ATOMIC_ACQUIRE) : 0;
   const bool hdr_ok = !MDBM || __atomic_load_n(&sc.hflags[1], __ATOMIC_ACQUIRE) != 0;
   // mdbm, a last key line at EOF after other records: the previous record's value (rare; a
   // second synchronisation only then)
-  if (MDBM && e == hipSuccess && hdr_ok && __atomic_load_n(&sc.hflags[2], __ATOMIC_ACQUIRE) && recs && n >= 2 &&
+  if (MDBM && tr.ok() && hdr_ok && __atomic_load_n(&sc.hflags[2], __ATOMIC_ACQUIRE) && recs && n >= 2 &&
       n <= cap) {
     tr(hipMemcpyAsync(&recs[n - 1].val_off, &recs[n - 2].val_off, 16, hipMemcpyDeviceToDevice, stream));
     tr(hipStreamSynchronize(stream));
   }
-  if (sc.bytes > kScratchKeep) {  // the stream is synchronised: no kernel still reads it
-    (void)hipFree(sc.p);
-    sc.p = nullptr;
-    sc.bytes = 0;
-  }
-  *herr = e;
-  if (e != hipSuccess) return K2H_AMD_EHIP;
+  sc.buf.release_above(kScratchKeep);
+  *herr = tr.e;
+  if (!tr.ok()) return K2H_AMD_EHIP;
   if (!hdr_ok) return K2H_AMD_EINVAL;  // k2himport: "error: not a mdbm file."
   *count = n;
   return (recs && n > cap) ? K2H_AMD_EINVAL : K2H_AMD_OK;

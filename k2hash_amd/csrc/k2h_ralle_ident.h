@@ -1,21 +1,21 @@
 // k2hash_amd -- a blob's identity as the kernels that sort blobs by their stored hash hold and
 // compare it (k2h_ralledata_dedup.hip, k2h_ralledata_diff.hip, k2h_ralledata_subkeys.hip): the
 // side record a gather leaves per participant, the end-aligned 16-byte compare of two byte ranges
-// of one length, and the number of hash bits the pairs are sorted by.  Below those, the join's
-// machinery in the form k2h_ralledata_subkeys.hip launches it: the kernel that lays the pairs
-// out for the sort, the mark kernel and max-scan operator, the backward walk to the last held
-// entry of an identity, and the per-device scratch.  k2h_ralledata_dedup.hip and
-// k2h_ralledata_diff.hip, from which these were lifted, launch the same ones.
+// of one length.  Below those, the join's machinery in the form k2h_ralledata_subkeys.hip
+// launches it: the kernel that lays the pairs out for the sort, the mark kernel and max-scan
+// operator, and the backward walk to the last held entry of an identity.
+// k2h_ralledata_dedup.hip and k2h_ralledata_diff.hip, from which these were lifted, launch the
+// same ones.  The number of hash bits the pairs are sorted by and the launchers' scratch are in
+// k2h_layout.h and k2h_scratch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stddef.h>
 #include <stdint.h>
 
-#include <mutex>
-
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
+#include "k2h_scratch.h"
 
 namespace k2h {
 
@@ -50,20 +50,6 @@ __device__ __forceinline__ bool same_key(const uint8_t* a, const uint8_t* b, uin
 __device__ __forceinline__ uint64_t ralle_shfl_u64(uint64_t v, int src) {
   const uint32_t lo = __shfl((uint32_t)v, src), hi = __shfl((uint32_t)(v >> 32), src);
   return pack2(lo, hi);
-}
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// The low hash bits the pairs are sorted by: 8 more than the blobs' number has, in whole
-// bytes (the library sorts a byte per pass), at least 16.  Equal hashes are neighbours under
-// any number of bits, and the sort stays stable; with 8 spare bits about one pair of neighbours
-// in 256 shares the sorted bits without sharing the hash, and the walk steps over those.  At
-// 8 Mi blobs this is 32 bits, half the passes of a 64-bit sort.
-inline int sort_bits_for(uint64_t n) {
-  int bits = 0;
-  while (bits < 64 && (n - 1) >> bits) ++bits;
-  bits = (bits + 8 + 7) / 8 * 8;
-  return bits < 16 ? 16 : bits > 64 ? 64 : bits;
 }
 
 constexpr int kIdentBlobs = 256;  // gather / compact: blobs per 256-thread block, one per thread
@@ -128,38 +114,5 @@ __device__ __forceinline__ uint32_t last_held(const uint64_t* __restrict__ keys,
   }
   return kNone;
 }
-
-// A launcher's temporaries: one grow-only buffer per device, held across calls under a
-// per-device lock.  The kernels still use the buffer after an asynchronous call has returned,
-// so each call leaves an event behind and the next call's stream waits for it before it writes.
-struct RalleScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-  // Under mu: at least `total` bytes at p, and `stream` behind the last call's event.  Returns
-  // a K2H_AMD_* code (the HIP error in *herr).
-  int reserve(size_t total, hipStream_t stream, hipError_t* herr) {
-    hipError_t e = hipSuccess;
-    if (!done) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-    if (e == hipSuccess && bytes < total) {
-      if (p) e = hipFree(p);  // waits for the device: no earlier call's kernel still uses it
-      p = nullptr;
-      bytes = 0;
-      const hipError_t a = e == hipSuccess ? hipMalloc(&p, total) : e;
-      if (a == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        p = nullptr;
-        *herr = a;
-        return K2H_AMD_ENOMEM;
-      }
-      if (e == hipSuccess) e = a;
-      if (e == hipSuccess) bytes = total;
-    }
-    if (e == hipSuccess) e = hipStreamWaitEvent(stream, done, 0);  // never recorded: no wait
-    *herr = e;
-    return e == hipSuccess ? K2H_AMD_OK : K2H_AMD_EHIP;
-  }
-};
 
 }  // namespace k2h

@@ -44,6 +44,7 @@
 
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
+#include "k2h_layout.h"
 #include "k2h_ralle_header.h"
 #include "k2h_ralle_pieces.h"
 
@@ -59,8 +60,6 @@ constexpr int kArcSlot = 112;               // LDS bytes per record header: 104,
 constexpr int kArcImg = kArcHdr + kArcSlot * kArcBlobs + kArcPool + 16;
 constexpr int kArcSpanMax = kScom * kArcBlobs + kArcHullMax;  // headers, stream bytes
 constexpr int kArcPieces = kArcSpanMax / 16 + 2;
-constexpr int kArcCounters = 64;  // the sizing kernel counts into this many words, each on a 64-byte line
-constexpr size_t kArcCounterBytes = 64 * kArcCounters;
 
 // szCommand of a SET_ALL record: "\nK2H_SET_ALL" and four 0x00 bytes (lib/k2hcommand.h:36-45).
 constexpr uint64_t kCmd0 = 0x5445535F48324B0Aull;  // "\nK2H_SET"
@@ -95,7 +94,8 @@ __device__ __forceinline__ void load_lens_pos(const uint8_t* p, uint64_t (&f)[10
 }
 
 // rec_off[i] = the record size of blob i, 0 for a blob that yields none; entry n is 0 (entry n
-// of the exclusive sum is the total).  Counts the records into the kArcCounters words.
+// of the exclusive sum is the total).  Counts the records into word 0 of the counter lines
+// (k2h_layout.h).
 __global__ __launch_bounds__(256) void scom_archive_size_kernel(const uint8_t* __restrict__ blobs, uint64_t size,
                                                                 const uint64_t* __restrict__ off, uint64_t n,
                                                                 const uint8_t* __restrict__ keep,
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void scom_archive_size_kernel(const uint8_t* _
   const unsigned long long m = __ballot(v != 0);
   if ((threadIdx.x & 63u) == 0 && m) {
     const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    atomicAdd(counters + 8 * (wave % kArcCounters), (unsigned long long)__popcll(m));
+    atomicAdd(counters + 8 * (wave % kCounterLines), (unsigned long long)__popcll(m));
   }
 }
 
@@ -365,8 +365,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void s
   }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // Returns a K2H_AMD_* code (the HIP error, if any, in *herr) and synchronises the stream once
@@ -384,9 +382,9 @@ int launch_ralledata_archive(const void* blobs, uint64_t size, const uint64_t* b
   uint8_t* tmp = nullptr;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, rec_off, rec_off, n + 1, stream));
   const size_t counters_at = align256(scan_bytes ? scan_bytes : 1);
-  if (e == hipSuccess) tr(hipMallocAsync((void**)&tmp, counters_at + kArcCounterBytes, stream));
+  if (e == hipSuccess) tr(hipMallocAsync((void**)&tmp, counters_at + kCounterBytes, stream));
   unsigned long long* counters = (unsigned long long*)(tmp + counters_at);
-  if (e == hipSuccess) tr(hipMemsetAsync(counters, 0, kArcCounterBytes, stream));
+  if (e == hipSuccess) tr(hipMemsetAsync(counters, 0, kCounterBytes, stream));
   if (e == hipSuccess) {
     scom_archive_size_kernel<<<(unsigned)grid_s, 256, 0, stream>>>((const uint8_t*)blobs, size, blob_off, n, keep,
                                                                   rec_off, counters);
@@ -394,17 +392,15 @@ int launch_ralledata_archive(const void* blobs, uint64_t size, const uint64_t* b
   }
   if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, rec_off, rec_off, n + 1, stream));
   uint64_t tot = 0;
-  unsigned long long counts[8 * kArcCounters];
+  unsigned long long counts[kCounterBytes / 8];
   if (e == hipSuccess) tr(hipMemcpyAsync(&tot, rec_off + n, 8, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipMemcpyAsync(counts, counters, kArcCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (e == hipSuccess) tr(hipMemcpyAsync(counts, counters, kCounterBytes, hipMemcpyDeviceToHost, stream));
   if (tmp) tr(hipFreeAsync(tmp, stream));
   if (e == hipSuccess) tr(hipStreamSynchronize(stream));
   int rc = K2H_AMD_OK;
   if (e == hipSuccess) {
-    uint64_t recs = 0;
-    for (int c = 0; c < kArcCounters; ++c) recs += counts[8 * c];
     *total = tot;
-    if (records) *records = recs;
+    if (records) *records = counter_sum(counts, 0);
     if (out && tot > out_cap) {
       rc = K2H_AMD_EINVAL;
     } else if (out && tot) {

@@ -23,6 +23,7 @@
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
 #include "k2h_ralle_header.h"
+#include "k2h_scratch.h"
 
 namespace k2h {
 namespace {
@@ -301,20 +302,16 @@ __global__ __launch_bounds__(256) void ralledata_select_copy_kernel(
   }
 }
 
-// The select's temporaries: one grow-only buffer per device, held across calls under a
-// per-device lock (the pattern of ScanScratch, k2h_import_dev.hip): per tile of kSelBlobs
-// blobs its kept bytes and count, their scans, and the scan's own storage -- 32 bytes per 256
-// blobs.  The copy kernel still reads the buffer after the call has returned, so each call
-// leaves an event behind and the next call's stream waits for it before it writes.
-struct SelScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-};
-SelScratch g_sel[64];
+// The select's temporaries (k2h_scratch.h): per tile of kSelBlobs blobs its kept bytes and
+// count, their scans, and the scan's own storage -- 32 bytes per 256 blobs.  The copy kernel
+// still reads the buffer after the call has returned.
+PerDevice<> g_sel;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct SelCols {
+  uint64_t *tb, *tc, *sb, *scn;
+  void* tmp;
+  size_t total;
+};
 
 }  // namespace
 
@@ -339,78 +336,57 @@ int launch_ralledata_select(const void* blobs, uint64_t size, const uint64_t* bl
   if (n == 0) return K2H_AMD_OK;
   const uint64_t nt = (n + kSelBlobs - 1) / kSelBlobs;
   if (nt > 0x7FFFFFFFull) return K2H_AMD_EINVAL;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  FirstError tr;
+  DeviceScratch* const sc = g_sel.current(tr);
   size_t tmp_bytes = 0;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
-  if (e != hipSuccess) {
-    *herr = e;
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
-  const size_t col = align256((nt + 1) * 8);
-  const size_t total = 4 * col + align256(tmp_bytes);
-  SelScratch& sc = g_sel[dev];
-  std::lock_guard<std::mutex> lk(sc.mu);
-  if (!sc.done) tr(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-  if (e == hipSuccess && sc.bytes < total) {
-    if (sc.p) tr(hipFree(sc.p));  // waits for the device: no earlier copy kernel still reads it
-    sc.p = nullptr;
-    sc.bytes = 0;
-    const hipError_t a = e == hipSuccess ? hipMalloc(&sc.p, total) : e;
-    if (a == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      sc.p = nullptr;
-      *herr = a;
-      return K2H_AMD_ENOMEM;
-    }
-    tr(a);
-    if (e == hipSuccess) sc.bytes = total;
-  }
-  if (e == hipSuccess) tr(hipStreamWaitEvent(stream, sc.done, 0));  // never recorded: no wait
-  if (e != hipSuccess) {
-    *herr = e;
-    return K2H_AMD_EHIP;
-  }
-  uint8_t* base = (uint8_t*)sc.p;
-  uint64_t* tb = (uint64_t*)base;
-  uint64_t* tc = (uint64_t*)(base + col);
-  uint64_t* sb = (uint64_t*)(base + 2 * col);
-  uint64_t* scn = (uint64_t*)(base + 3 * col);
-  void* tmp = base + 4 * col;
+  auto layout = [&](void* base) {
+    Carver c(base);
+    SelCols k;
+    k.tb = c.take<uint64_t>(nt + 1);
+    k.tc = c.take<uint64_t>(nt + 1);
+    k.sb = c.take<uint64_t>(nt + 1);
+    k.scn = c.take<uint64_t>(nt + 1);
+    k.tmp = c.bytes(tmp_bytes);
+    k.total = c.total();
+    return k;
+  };
+  std::lock_guard<std::mutex> lk(sc->mu);
+  if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
+  const SelCols k = layout(sc->p);
   // entry nt of the sums is 0, so entry nt of the exclusive scans is the total
-  tr(hipMemsetAsync(tb + nt, 0, 8, stream));
-  tr(hipMemsetAsync(tc + nt, 0, 8, stream));
-  if (e == hipSuccess) {
-    ralledata_select_sum_kernel<<<(unsigned)nt, kSelBlobs, 0, stream>>>(blob_off, size, n, keep, tb, tc);
+  tr(hipMemsetAsync(k.tb + nt, 0, 8, stream));
+  tr(hipMemsetAsync(k.tc + nt, 0, 8, stream));
+  if (tr.ok()) {
+    ralledata_select_sum_kernel<<<(unsigned)nt, kSelBlobs, 0, stream>>>(blob_off, size, n, keep, k.tb, k.tc);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, tb, sb, nt + 1, stream));
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, tc, scn, nt + 1, stream));
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tmp_bytes, k.tb, k.sb, nt + 1, stream));
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tmp_bytes, k.tc, k.scn, nt + 1, stream));
   uint64_t tot[2] = {0, 0};
-  if (e == hipSuccess) tr(hipMemcpyAsync(&tot[0], sb + nt, 8, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipMemcpyAsync(&tot[1], scn + nt, 8, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipStreamSynchronize(stream));
+  if (tr.ok()) tr(hipMemcpyAsync(&tot[0], k.sb + nt, 8, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(hipMemcpyAsync(&tot[1], k.scn + nt, 8, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(hipStreamSynchronize(stream));
   int rc = K2H_AMD_OK;
-  if (e == hipSuccess) {
+  if (tr.ok()) {
     *kept_bytes = tot[0];
     *kept = tot[1];
     if (out && tot[0] > out_cap) {
       rc = K2H_AMD_EINVAL;
     } else if (out) {
       ralledata_select_copy_kernel<<<(unsigned)nt, kSelBlobs, 0, stream>>>((const uint8_t*)blobs, size, blob_off, n,
-                                                                          keep, sb, scn, nt, (uint8_t*)out, out_off,
+                                                                          keep, k.sb, k.scn, nt, (uint8_t*)out, out_off,
                                                                           index);
       tr(hipGetLastError());
-      if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
+      if (tr.ok()) tr(sc->mark_done(stream));
     }
   }
-  *herr = e;
-  return e != hipSuccess ? K2H_AMD_EHIP : rc;
+  *herr = tr.e;
+  return !tr.ok() ? K2H_AMD_EHIP : rc;
 }
 
 }  // namespace k2h

@@ -60,7 +60,6 @@ namespace {
 
 constexpr int kDedupBlobs = 256;         // gather / compact: blobs per 256-thread block, one per thread
 constexpr int kResolveBlock = 256;       // resolve: sorted positions per block, one per thread
-constexpr int kCounters = 64;            // resolve counts into this many words, each on a 64-byte line of its own
 
 // The mtime rule (k2h_amd_ralledata_dedup_mtime) keeps a participant's mtime next to its side
 // record, in an array of its own so that the side record and the plain rule's kernels stay what
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(256) void ralledata_dedup_gather_kernel(
 
 // keys / idx: the pairs, sorted by the hash bits under `mask` (sort_bits_for).  Writes
 // keep[i] = 0 for a superseded blob and by[i] for every blob that has a later one of its
-// identity; counts the superseded into the kCounters words of `dropped` (their sum is the
+// identity; counts the superseded into the counter lines of `dropped`, word 0 (their sum is the
 // count).  MT: the mtime rule in place of the attrs rule -- i is superseded by j when i has
 // no mtime, or both have one and m_i < m_j and m_i < pts (both strict).
 template <bool MT>
@@ -165,21 +164,25 @@ __global__ __launch_bounds__(kResolveBlock) void ralledata_dedup_resolve_kernel(
   const unsigned long long m = __ballot(drop);
   if ((threadIdx.x & 63u) == 0 && m) {
     const uint32_t wave = blockIdx.x * (kResolveBlock / 64) + (threadIdx.x >> 6);
-    atomicAdd(dropped + 8 * (wave % kCounters), (unsigned long long)__popcll(m));
+    atomicAdd(dropped + 8 * (wave % kCounterLines), (unsigned long long)__popcll(m));
   }
 }
 
-// The call's temporaries (RalleScratch, k2h_ralle_ident.h: one grow-only buffer per device under
-// a lock, with the event the next call's stream waits for) -- 56 bytes per blob (two key and two
-// index columns, the side records), the tile counts and their scan, the counters, and the
-// library's own storage; the mtime rule adds 16 bytes per blob behind them.
-RalleScratch g_dedup[64];
+// The call's temporaries (k2h_scratch.h) -- 56 bytes per blob (two key and two index columns, the
+// side records), the tile counts and their scan, the counters, and the library's own storage;
+// the mtime rule adds 16 bytes per blob behind them.
+PerDevice<> g_dedup;
 
-constexpr size_t kCounterBytes = 64 * kCounters;
-
-}  // namespace
-
-namespace {
+struct DedupCols {
+  uint64_t *keys_in, *keys_out;  // keys_out: first the blobs' hashes by blob index, then the sorted keys
+  uint32_t *idx_in, *idx_out;
+  Side* side;
+  uint64_t *tile_count, *tile_base;
+  unsigned long long* counter;
+  void* tmp;
+  Mtime* mt;  // the mtime rule only, behind everything else: the plain rule's layout stays
+  size_t total;
+};
 
 // Both entry points; pts == NULL: the attrs rule.
 int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const uint8_t* consider,
@@ -187,84 +190,79 @@ int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uin
                  hipError_t* herr) {
   *herr = hipSuccess;
   const uint64_t nt = (n + kDedupBlobs - 1) / kDedupBlobs;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  FirstError tr;
+  DeviceScratch* const sc = g_dedup.current(tr);
   size_t scan_bytes = 0, sort_bytes = 0;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
   const int sort_bits = sort_bits_for(n);
   tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
-  if (e != hipSuccess) {
-    *herr = e;
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
-  const size_t c8 = align256(n * 8), c4 = align256(n * 4), cs = align256(n * sizeof(Side)), ct = align256((nt + 1) * 8);
-  const size_t tmp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-  const size_t cm = pts ? align256(n * sizeof(Mtime)) : 0;  // behind everything else: the plain rule's layout stays
-  const size_t total = 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes + align256(tmp_bytes) + cm;
-  RalleScratch& sc = g_dedup[dev];
-  std::lock_guard<std::mutex> lk(sc.mu);
-  if (const int rc = sc.reserve(total, stream, herr)) return rc;
-  uint8_t* base = (uint8_t*)sc.p;
-  uint64_t* keys_in = (uint64_t*)base;
-  uint64_t* keys_out = (uint64_t*)(base + c8);  // first the blobs' hashes by blob index, then the sorted keys
-  uint32_t* idx_in = (uint32_t*)(base + 2 * c8);
-  uint32_t* idx_out = (uint32_t*)(base + 2 * c8 + c4);
-  Side* side = (Side*)(base + 2 * c8 + 2 * c4);
-  uint64_t* tile_count = (uint64_t*)(base + 2 * c8 + 2 * c4 + cs);
-  uint64_t* tile_base = (uint64_t*)(base + 2 * c8 + 2 * c4 + cs + ct);
-  unsigned long long* counter = (unsigned long long*)(base + 2 * c8 + 2 * c4 + cs + 2 * ct);
-  void* tmp = base + 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes;
-  Mtime* mt = (Mtime*)(base + 2 * c8 + 2 * c4 + cs + 2 * ct + kCounterBytes + align256(tmp_bytes));
+  auto layout = [&](void* base) {
+    Carver c(base);
+    DedupCols k;
+    k.keys_in = c.take<uint64_t>(n);
+    k.keys_out = c.take<uint64_t>(n);
+    k.idx_in = c.take<uint32_t>(n);
+    k.idx_out = c.take<uint32_t>(n);
+    k.side = c.take<Side>(n);
+    k.tile_count = c.take<uint64_t>(nt + 1);
+    k.tile_base = c.take<uint64_t>(nt + 1);
+    k.counter = (unsigned long long*)c.bytes(kCounterBytes);
+    k.tmp = c.bytes(scan_bytes > sort_bytes ? scan_bytes : sort_bytes);
+    k.mt = pts ? c.take<Mtime>(n) : nullptr;
+    k.total = c.total();
+    return k;
+  };
+  std::lock_guard<std::mutex> lk(sc->mu);
+  if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
+  const DedupCols k = layout(sc->p);
   // entry nt of the counts is 0, so entry nt of their exclusive scan is the participants' number
-  tr(hipMemsetAsync(tile_count + nt, 0, 8, stream));
-  tr(hipMemsetAsync(counter, 0, kCounterBytes, stream));
-  if (e == hipSuccess) {
+  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
+  if (tr.ok()) {
     if (pts)
       ralledata_dedup_gather_kernel<true><<<(unsigned)nt, kDedupBlobs, kWalkLdsBytes, stream>>>(
-          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, keys_out, side, tile_count, mt);
+          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, k.keys_out, k.side, k.tile_count, k.mt);
     else
       ralledata_dedup_gather_kernel<false><<<(unsigned)nt, kDedupBlobs, 0, stream>>>(
-          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, keys_out, side, tile_count, nullptr);
+          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, k.keys_out, k.side, k.tile_count, nullptr);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, tile_count, tile_base, nt + 1, stream));
-  if (e == hipSuccess) {
-    ralle_compact_kernel<kDedupBlobs><<<(unsigned)nt, kDedupBlobs, 0, stream>>>(keep, keys_out, n, tile_base, nt, 0,
-                                                                               keys_in, idx_in);
+  if (tr.ok())
+    tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, scan_bytes, k.tile_count, k.tile_base, nt + 1, stream));
+  if (tr.ok()) {
+    ralle_compact_kernel<kDedupBlobs><<<(unsigned)nt, kDedupBlobs, 0, stream>>>(keep, k.keys_out, n, k.tile_base, nt, 0,
+                                                                               k.keys_in, k.idx_in);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess)
-    tr(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint64_t*)keys_in, keys_out,
-                                          (const uint32_t*)idx_in, idx_out, n, 0, sort_bits, stream));
-  if (e == hipSuccess) {
+  if (tr.ok())
+    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
+                                          (const uint32_t*)k.idx_in, k.idx_out, n, 0, sort_bits, stream));
+  if (tr.ok()) {
     const uint64_t grid = (n + kResolveBlock - 1) / kResolveBlock;
-    const uint64_t mask = sort_bits == 64 ? ~0ull : (1ull << sort_bits) - 1;
+    const uint64_t mask = sort_mask(sort_bits);
     if (pts)
       ralledata_dedup_resolve_kernel<true><<<(unsigned)grid, kResolveBlock, 0, stream>>>(
-          (const uint8_t*)blobs, keys_out, idx_out, n, mask, side, keep, by, counter,
-          MtimeRule{mt, pts->sec, pts->nsec});
+          (const uint8_t*)blobs, k.keys_out, k.idx_out, n, mask, k.side, keep, by, k.counter,
+          MtimeRule{k.mt, pts->sec, pts->nsec});
     else
       ralledata_dedup_resolve_kernel<false><<<(unsigned)grid, kResolveBlock, 0, stream>>>(
-          (const uint8_t*)blobs, keys_out, idx_out, n, mask, side, keep, by, counter, MtimeRule{nullptr, 0, 0});
+          (const uint8_t*)blobs, k.keys_out, k.idx_out, n, mask, k.side, keep, by, k.counter, MtimeRule{nullptr, 0, 0});
     tr(hipGetLastError());
   }
-  unsigned long long counts[8 * kCounters];
-  if (e == hipSuccess && dropped) tr(hipMemcpyAsync(counts, counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
-  if (e == hipSuccess && dropped) {
+  unsigned long long counts[kCounterBytes / 8];
+  if (tr.ok() && dropped) tr(hipMemcpyAsync(counts, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(sc->mark_done(stream));
+  if (tr.ok() && dropped) {
     tr(hipStreamSynchronize(stream));
-    uint64_t sum = 0;
-    for (int c = 0; c < kCounters; ++c) sum += counts[8 * c];
-    if (e == hipSuccess) *dropped = sum;
+    if (tr.ok()) *dropped = counter_sum(counts, 0);
   }
-  *herr = e;
-  return e != hipSuccess ? K2H_AMD_EHIP : K2H_AMD_OK;
+  *herr = tr.e;
+  return !tr.ok() ? K2H_AMD_EHIP : K2H_AMD_OK;
 }
 
 }  // namespace

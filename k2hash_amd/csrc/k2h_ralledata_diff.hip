@@ -62,8 +62,6 @@ namespace {
 constexpr int kDiffBlobs = 256;         // gather / compact / compare: blobs per 256-thread block
 constexpr int kDiffResolveBlock = 256;  // resolve: sorted positions per block, one per thread
 constexpr int kDiffWaveBytes = 128;     // a pair with more bytes to compare than this is compared by its wave
-constexpr int kDiffCounters = 64;       // compare counts into this many 64-byte lines, four words in each
-constexpr size_t kDiffCounterBytes = 64 * kDiffCounters;
 
 // Side::attrs of this file's gather.
 constexpr uint64_t kFlagAttrs = 1;    // attrs_length != 0
@@ -249,7 +247,7 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
 
 // One lane per blob of A; work[i], written for every FOUND blob: the matched blob of B when
 // some segment of the pair has equal non-zero lengths, else kNone.  ORs the differ bits of those segments into rel[i], and
-// counts {PART, FOUND, FOUND without a differ bit, APPLY} into the kDiffCounters lines.
+// counts {PART, FOUND, FOUND without a differ bit, APPLY} into the counter lines (four words in each).
 __global__ __launch_bounds__(kDiffBlobs) void ralledata_diff_compare_kernel(DiffStream a, uint64_t na, DiffStream b,
                                                                             const uint32_t* __restrict__ work,
                                                                             uint8_t* __restrict__ rel,
@@ -308,7 +306,7 @@ __global__ __launch_bounds__(kDiffBlobs) void ralledata_diff_compare_kernel(Diff
   if (lane == 0 && m0) {
     // one line per wave, neighbouring waves on different lines (as the dedup's resolve counts)
     const uint32_t wave = blockIdx.x * (kDiffBlobs / 64) + (threadIdx.x >> 6);
-    unsigned long long* c = counter + 8 * (wave % kDiffCounters);
+    unsigned long long* c = counter + 8 * (wave % kCounterLines);
     atomicAdd(c, (unsigned long long)__popcll(m0));
     if (m1) atomicAdd(c + 1, (unsigned long long)__popcll(m1));
     if (m2) atomicAdd(c + 2, (unsigned long long)__popcll(m2));
@@ -318,14 +316,25 @@ __global__ __launch_bounds__(kDiffBlobs) void ralledata_diff_compare_kernel(Diff
 static_assert(K2H_AMD_DIFF_SKEY == K2H_AMD_DIFF_VAL << 1 && K2H_AMD_DIFF_ATTRS == K2H_AMD_DIFF_VAL << 2,
               "the three differ bits in segment order");
 
-// The call's temporaries: one grow-only buffer per device under a lock with its event
-// (RalleScratch, k2h_ralle_ident.h).  With n = na + nb: two key and two index columns and the side
+// The call's temporaries (k2h_scratch.h).  With n = na + nb: two key and two index columns and the side
 // records (56 n bytes), a participant byte per blob, the tile counts and their scan, the
 // counters and the library's own storage; with times 16 n more for the mtimes.  The scan column
 // and the work items need none of their own: after the sort its input columns are free, and the
 // mark column takes the index column's place, the scanned positions and the na work items the
 // two halves of the key column's.
-RalleScratch g_diff[64];
+PerDevice<> g_diff;
+
+struct DiffCols {
+  uint64_t *keys_in, *keys_out;  // keys_out: first the blobs' hashes by index, then the sorted keys
+  uint32_t *idx_in, *idx_out;
+  Side* side;
+  uint8_t* part;
+  uint64_t *tile_count, *tile_base;
+  unsigned long long* counter;
+  void* tmp;
+  DiffMtime* mt;  // with times only, behind everything else
+  size_t total;
+};
 
 }  // namespace
 
@@ -338,13 +347,8 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
   *herr = hipSuccess;
   const uint64_t n = na + nb;
   const uint64_t nt = (n + kDiffBlobs - 1) / kDiffBlobs;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  FirstError tr;
+  DeviceScratch* const sc = g_diff.current(tr);
   size_t scan_bytes = 0, sort_bytes = 0, max_bytes = 0;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
   const int sort_bits = sort_bits_for(n);
@@ -352,104 +356,97 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
   tr(hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                        RalleMaxU32(), n, stream));
-  if (e != hipSuccess) {
-    *herr = e;
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
-  const size_t c8 = align256(n * 8), c4 = align256(n * 4), cs = align256(n * sizeof(Side)), ct = align256((nt + 1) * 8);
-  const size_t cp = align256(n);
   size_t tmp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
   if (max_bytes > tmp_bytes) tmp_bytes = max_bytes;
-  const size_t cm = times ? align256(n * sizeof(DiffMtime)) : 0;
-  const size_t total = 2 * c8 + 2 * c4 + cs + cp + 2 * ct + kDiffCounterBytes + align256(tmp_bytes) + cm;
-  RalleScratch& sc = g_diff[dev];
-  std::lock_guard<std::mutex> lk(sc.mu);
-  if (const int rc = sc.reserve(total, stream, herr)) return rc;
-  uint8_t* at = (uint8_t*)sc.p;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = at;
-    at += bytes;
-    return p;
+  auto layout = [&](void* base) {
+    Carver c(base);
+    DiffCols k;
+    k.keys_in = c.take<uint64_t>(n);
+    k.keys_out = c.take<uint64_t>(n);
+    k.idx_in = c.take<uint32_t>(n);
+    k.idx_out = c.take<uint32_t>(n);
+    k.side = c.take<Side>(n);
+    k.part = c.take<uint8_t>(n);
+    k.tile_count = c.take<uint64_t>(nt + 1);
+    k.tile_base = c.take<uint64_t>(nt + 1);
+    k.counter = (unsigned long long*)c.bytes(kCounterBytes);
+    k.tmp = c.bytes(tmp_bytes);
+    k.mt = c.take<DiffMtime>(times ? n : 0);
+    k.total = c.total();
+    return k;
   };
-  uint64_t* keys_in = (uint64_t*)take(c8);
-  uint64_t* keys_out = (uint64_t*)take(c8);  // first the blobs' hashes by index, then the sorted keys
-  uint32_t* idx_in = (uint32_t*)take(c4);
-  uint32_t* idx_out = (uint32_t*)take(c4);
-  Side* side = (Side*)take(cs);
-  uint8_t* part = take(cp);
-  uint64_t* tile_count = (uint64_t*)take(ct);
-  uint64_t* tile_base = (uint64_t*)take(ct);
-  unsigned long long* counter = (unsigned long long*)take(kDiffCounterBytes);
-  void* tmp = take(align256(tmp_bytes));
-  DiffMtime* mt = (DiffMtime*)take(cm);
+  std::lock_guard<std::mutex> lk(sc->mu);
+  if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
+  const DiffCols k = layout(sc->p);
   // free once the sort has read them, its input columns: the mark column takes the index column's
   // place, the scanned positions the first half of the key column's and the na work items the
   // second (n * 4 >= na * 4 bytes)
-  uint32_t* mark = idx_in;
-  uint32_t* last_b = (uint32_t*)keys_in;
+  uint32_t* mark = k.idx_in;
+  uint32_t* last_b = (uint32_t*)k.keys_in;
   uint32_t* work = last_b + n;
 
   const DiffStream sa{(const uint8_t*)a_blobs, a_size, a_off, a_consider};
   const DiffStream sb{(const uint8_t*)b_blobs, b_size, b_off, b_consider};
-  DiffTimes tm{mt, 0, 0, 0, 0};
-  if (times) tm = DiffTimes{mt, times->pts.sec, times->pts.nsec, times->now.sec, times->now.nsec};
+  DiffTimes tm{k.mt, 0, 0, 0, 0};
+  if (times) tm = DiffTimes{k.mt, times->pts.sec, times->pts.nsec, times->now.sec, times->now.nsec};
   // entry nt of the counts is 0, so entry nt of their exclusive scan is the participants' number
-  tr(hipMemsetAsync(tile_count + nt, 0, 8, stream));
-  tr(hipMemsetAsync(counter, 0, kDiffCounterBytes, stream));
+  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
   if (seen && nb) tr(hipMemsetAsync(seen, 0, nb, stream));
-  if (e == hipSuccess) {
+  if (tr.ok()) {
     if (times)
       ralledata_diff_gather_kernel<true><<<(unsigned)nt, kDiffBlobs, kWalkLdsBytes, stream>>>(
-          sa, na, sb, nb, part, keys_out, side, tile_count, rel, match, tm);
+          sa, na, sb, nb, k.part, k.keys_out, k.side, k.tile_count, rel, match, tm);
     else
-      ralledata_diff_gather_kernel<false><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(sa, na, sb, nb, part, keys_out,
-                                                                                 side, tile_count, rel, match, tm);
+      ralledata_diff_gather_kernel<false><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(sa, na, sb, nb, k.part, k.keys_out,
+                                                                                 k.side, k.tile_count, rel, match, tm);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, tile_count, tile_base, nt + 1, stream));
-  if (e == hipSuccess) {
-    ralle_compact_kernel<kDiffBlobs><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(part, keys_out, n, tile_base, nt, 0,
-                                                                             keys_in, idx_in);
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, scan_bytes, k.tile_count, k.tile_base, nt + 1, stream));
+  if (tr.ok()) {
+    ralle_compact_kernel<kDiffBlobs><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(k.part, k.keys_out, n, k.tile_base, nt, 0,
+                                                                             k.keys_in, k.idx_in);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess)
-    tr(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint64_t*)keys_in, keys_out,
-                                          (const uint32_t*)idx_in, idx_out, n, 0, sort_bits, stream));
-  if (e == hipSuccess) {
-    ralle_mark_kernel<256><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(idx_out, n, nb, mark);
+  if (tr.ok())
+    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
+                                          (const uint32_t*)k.idx_in, k.idx_out, n, 0, sort_bits, stream));
+  if (tr.ok()) {
+    ralle_mark_kernel<256><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(k.idx_out, n, nb, mark);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess)
-    tr(hipcub::DeviceScan::InclusiveScan(tmp, max_bytes, (const uint32_t*)mark, last_b, RalleMaxU32(), n, stream));
-  if (e == hipSuccess) {
+  if (tr.ok())
+    tr(hipcub::DeviceScan::InclusiveScan(k.tmp, max_bytes, (const uint32_t*)mark, last_b, RalleMaxU32(), n, stream));
+  if (tr.ok()) {
     const uint64_t grid = (n + kDiffResolveBlock - 1) / kDiffResolveBlock;
-    const uint64_t mask = sort_bits == 64 ? ~0ull : (1ull << sort_bits) - 1;
+    const uint64_t mask = sort_mask(sort_bits);
     if (times)
       ralledata_diff_resolve_kernel<true><<<(unsigned)grid, kDiffResolveBlock, 0, stream>>>(
-          sa, sb, nb, keys_out, idx_out, n, mask, last_b, side, rel, match, seen, work, tm);
+          sa, sb, nb, k.keys_out, k.idx_out, n, mask, last_b, k.side, rel, match, seen, work, tm);
     else
       ralledata_diff_resolve_kernel<false><<<(unsigned)grid, kDiffResolveBlock, 0, stream>>>(
-          sa, sb, nb, keys_out, idx_out, n, mask, last_b, side, rel, match, seen, work, tm);
+          sa, sb, nb, k.keys_out, k.idx_out, n, mask, last_b, k.side, rel, match, seen, work, tm);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) {
+  if (tr.ok()) {
     ralledata_diff_compare_kernel<<<(unsigned)((na + kDiffBlobs - 1) / kDiffBlobs), kDiffBlobs, 0, stream>>>(
-        sa, na, sb, work, rel, counter);
+        sa, na, sb, work, rel, k.counter);
     tr(hipGetLastError());
   }
-  unsigned long long host[8 * kDiffCounters];
-  if (e == hipSuccess && counts) tr(hipMemcpyAsync(host, counter, kDiffCounterBytes, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
-  if (e == hipSuccess && counts) {
+  unsigned long long host[kCounterBytes / 8];
+  if (tr.ok() && counts) tr(hipMemcpyAsync(host, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(sc->mark_done(stream));
+  if (tr.ok() && counts) {
     tr(hipStreamSynchronize(stream));
-    uint64_t sum[4] = {0, 0, 0, 0};
-    for (int c = 0; c < kDiffCounters; ++c)
-      for (int k = 0; k < 4; ++k) sum[k] += host[8 * c + k];
-    if (e == hipSuccess)
-      for (int k = 0; k < 4; ++k) counts[k] = sum[k];
+    if (tr.ok())
+      for (int w = 0; w < 4; ++w) counts[w] = counter_sum(host, w);
   }
-  *herr = e;
-  return e != hipSuccess ? K2H_AMD_EHIP : K2H_AMD_OK;
+  *herr = tr.e;
+  return !tr.ok() ? K2H_AMD_EHIP : K2H_AMD_OK;
 }
 
 }  // namespace k2h

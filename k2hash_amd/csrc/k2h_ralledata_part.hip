@@ -29,6 +29,7 @@
 
 #include "k2h_fnv_device.h"
 #include "k2h_kernels.h"
+#include "k2h_scratch.h"
 
 namespace k2h {
 namespace {
@@ -227,19 +228,16 @@ __global__ __launch_bounds__(kPartThreads) void ralledata_part_copy_kernel(
   }
 }
 
-// The call's temporaries: one grow-only buffer per device, held across calls under a per-device
-// lock, the pattern of the select's SelScratch (k2h_ralledata_check.hip).  The copy kernel still
-// reads the buffer after the call has returned, so each call leaves an event behind and the next
-// call's stream waits for it before it writes.
-struct PartScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-};
-PartScratch g_part[64];
+// The call's temporaries (k2h_scratch.h): the two histograms, the bounds, a part id per blob and
+// the scan's own storage.  The copy kernel still reads the buffer after the call has returned.
+PerDevice<> g_part;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct PartCols {
+  uint64_t *hc, *hb, *bounds;
+  uint16_t* ids;
+  void* tmp;
+  size_t total;
+};
 
 }  // namespace
 
@@ -254,68 +252,47 @@ int launch_ralledata_partition(const void* blobs, uint64_t size, const uint64_t*
   const uint64_t nt = (n + kPartBlobs - 1) / kPartBlobs;
   if (nt > 0x7FFFFFFFull / parts) return K2H_AMD_EINVAL;
   const uint64_t m = nt * parts;  // histogram entries; entry m of a scan is the total
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  FirstError tr;
+  DeviceScratch* const sc = g_part.current(tr);
   size_t tmp_bytes = 0;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, m + 1, stream));
-  if (e != hipSuccess) {
-    *herr = e;
+  if (!tr.ok()) {
+    *herr = tr.e;
     return K2H_AMD_EHIP;
   }
-  const size_t col = align256((m + 1) * 8), bnd = align256(2 * (parts + 1) * 8), idb = align256(n * 2);
-  const size_t total = 2 * col + bnd + idb + align256(tmp_bytes);
-  PartScratch& sc = g_part[dev];
-  std::lock_guard<std::mutex> lk(sc.mu);
-  if (!sc.done) tr(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-  if (e == hipSuccess && sc.bytes < total) {
-    if (sc.p) tr(hipFree(sc.p));  // waits for the device: no earlier copy kernel still reads it
-    sc.p = nullptr;
-    sc.bytes = 0;
-    const hipError_t a = e == hipSuccess ? hipMalloc(&sc.p, total) : e;
-    if (a == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      sc.p = nullptr;
-      *herr = a;
-      return K2H_AMD_ENOMEM;
-    }
-    tr(a);
-    if (e == hipSuccess) sc.bytes = total;
-  }
-  if (e == hipSuccess) tr(hipStreamWaitEvent(stream, sc.done, 0));  // never recorded: no wait
-  if (e != hipSuccess) {
-    *herr = e;
-    return K2H_AMD_EHIP;
-  }
-  uint8_t* base = (uint8_t*)sc.p;
-  uint64_t* hc = (uint64_t*)base;
-  uint64_t* hb = (uint64_t*)(base + col);
-  uint64_t* bounds = (uint64_t*)(base + 2 * col);
-  uint16_t* ids = (uint16_t*)(base + 2 * col + bnd);
-  void* tmp = base + 2 * col + bnd + idb;
+  auto layout = [&](void* base) {
+    Carver c(base);
+    PartCols k;
+    k.hc = c.take<uint64_t>(m + 1);
+    k.hb = c.take<uint64_t>(m + 1);
+    k.bounds = c.take<uint64_t>(2 * (parts + 1));
+    k.ids = c.take<uint16_t>(n);
+    k.tmp = c.bytes(tmp_bytes);
+    k.total = c.total();
+    return k;
+  };
+  std::lock_guard<std::mutex> lk(sc->mu);
+  if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
+  const PartCols k = layout(sc->p);
   // entry m of the histograms is 0, so entry m of the exclusive scans is the total
-  tr(hipMemsetAsync(hc + m, 0, 8, stream));
-  tr(hipMemsetAsync(hb + m, 0, 8, stream));
-  if (e == hipSuccess) {
+  tr(hipMemsetAsync(k.hc + m, 0, 8, stream));
+  tr(hipMemsetAsync(k.hb + m, 0, 8, stream));
+  if (tr.ok()) {
     ralledata_part_count_kernel<<<(unsigned)nt, kPartThreads, 0, stream>>>(
-        (const uint8_t*)blobs, size, blob_off, n, rule, part_ids, consider, nt, ids, part_out, hc, hb);
+        (const uint8_t*)blobs, size, blob_off, n, rule, part_ids, consider, nt, k.ids, part_out, k.hc, k.hb);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, hc, hc, m + 1, stream));
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, hb, hb, m + 1, stream));
-  if (e == hipSuccess) {
-    ralledata_part_bounds_kernel<<<1, kPartThreads, 0, stream>>>(hc, hb, nt, parts, bounds);
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tmp_bytes, k.hc, k.hc, m + 1, stream));
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tmp_bytes, k.hb, k.hb, m + 1, stream));
+  if (tr.ok()) {
+    ralledata_part_bounds_kernel<<<1, kPartThreads, 0, stream>>>(k.hc, k.hb, nt, parts, k.bounds);
     tr(hipGetLastError());
   }
   uint64_t host[2 * (K2H_AMD_PART_MAX + 1)];
-  if (e == hipSuccess) tr(hipMemcpyAsync(host, bounds, 2 * (parts + 1) * 8, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipStreamSynchronize(stream));
+  if (tr.ok()) tr(hipMemcpyAsync(host, k.bounds, 2 * (parts + 1) * 8, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(hipStreamSynchronize(stream));
   int rc = K2H_AMD_OK;
-  if (e == hipSuccess) {
+  if (tr.ok()) {
     for (uint32_t p = 0; p <= parts; ++p) {
       part_first[p] = host[p];
       part_byte[p] = host[parts + 1 + p];
@@ -326,13 +303,13 @@ int launch_ralledata_partition(const void* blobs, uint64_t size, const uint64_t*
       int id_bits = 1;  // the sort's keys are 0 .. parts
       while ((1u << id_bits) <= parts) ++id_bits;
       ralledata_part_copy_kernel<<<(unsigned)nt, kPartThreads, 0, stream>>>(
-          (const uint8_t*)blobs, blob_off, n, ids, hc, hb, nt, parts, id_bits, (uint8_t*)out, out_off, index);
+          (const uint8_t*)blobs, blob_off, n, k.ids, k.hc, k.hb, nt, parts, id_bits, (uint8_t*)out, out_off, index);
       tr(hipGetLastError());
-      if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
+      if (tr.ok()) tr(sc->mark_done(stream));
     }
   }
-  *herr = e;
-  return e != hipSuccess ? K2H_AMD_EHIP : rc;
+  *herr = tr.e;
+  return !tr.ok() ? K2H_AMD_EHIP : rc;
 }
 
 }  // namespace k2h

@@ -70,10 +70,8 @@ namespace {
 
 constexpr int kSkBlobs = 256;         // count / emit: blobs per 256-thread block, one per thread
 constexpr int kSkBlock = 256;         // every other kernel: items per block, one per thread
-constexpr int kSkCounters = 64;       // counts go into this many 64-byte lines, four words in each
-constexpr size_t kSkCounterBytes = 64 * kSkCounters;
 constexpr int kReachWaveEdges = 32;   // a frontier blob with more edges than this is followed by its wave
-constexpr size_t kSkPinnedBytes = kSkCounterBytes + 64;  // the counters, then one word
+constexpr size_t kSkPinnedBytes = kCounterBytes + 64;  // the counters, then one word
 
 struct SkStream {
   const uint8_t* blobs;
@@ -97,7 +95,7 @@ __device__ __forceinline__ void sk_count(unsigned long long* counter, int word, 
   const unsigned long long m = __ballot(x);
   if ((threadIdx.x & 63u) == 0 && m) {
     const uint32_t wave = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    atomicAdd(counter + 8 * (wave % kSkCounters) + word, (unsigned long long)__popcll(m));
+    atomicAdd(counter + 8 * (wave % kCounterLines) + word, (unsigned long long)__popcll(m));
   }
 }
 
@@ -294,17 +292,33 @@ __global__ __launch_bounds__(kSkBlock) void reach_final_kernel(const uint64_t* _
   sk_count(counter, 0, r);
 }
 
-// Both calls' temporaries (RalleScratch) and the pinned words their read-backs land in.
-struct SkScratch : RalleScratch {
+// Both calls' temporaries (k2h_scratch.h) and the pinned words their read-backs land in.
+struct SkScratch : DeviceScratch {
   void* pinned = nullptr;
 };
-SkScratch g_sk[64];
+PerDevice<SkScratch> g_sk;
 
-uint64_t sum_word(const unsigned long long* lines, int word) {
-  uint64_t s = 0;
-  for (int c = 0; c < kSkCounters; ++c) s += lines[8 * c + word];
-  return s;
-}
+struct CountCols {  // the count pass: a column of n + 1 counts, the counters, the scan's storage
+  uint64_t* cnt;
+  unsigned long long* counter;
+  void* tmp;
+  size_t total;
+};
+struct JoinCols {  // the join, over N = n + E entries
+  uint64_t *keys_in, *keys_out;  // keys_out: first the blobs' hashes by index, then the sorted keys
+  uint32_t *idx_in, *idx_out, *bound_s;
+  Side* side;
+  uint8_t* part;
+  uint64_t *tile_count, *tile_base;
+  unsigned long long* counter;
+  void* tmp;
+  size_t total;
+};
+struct ReachCols {
+  uint32_t *bits, *cur, *next;
+  unsigned long long* counter;  // the counter lines, then the frontier's size, one word per parity of the level
+  size_t total;
+};
 
 }  // namespace
 
@@ -319,52 +333,52 @@ int launch_ralledata_subkeys(const void* blobs, uint64_t size, const uint64_t* b
   *herr = hipSuccess;
   *why = 0;
   const uint64_t nt = (n + kSkBlobs - 1) / kSkBlobs;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
+  FirstError tr;
   auto done = [&]() {
-    *herr = e;
-    return e != hipSuccess ? K2H_AMD_EHIP : K2H_AMD_OK;
+    *herr = tr.e;
+    return !tr.ok() ? K2H_AMD_EHIP : K2H_AMD_OK;
   };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  SkScratch* const scp = g_sk.current(tr);
   size_t scan_bytes = 0;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, n + 1, stream));
-  if (e != hipSuccess) return done();
-  SkScratch& sc = g_sk[dev];
+  if (!tr.ok()) return done();
+  SkScratch& sc = *scp;
   std::lock_guard<std::mutex> lk(sc.mu);
   if (!sc.pinned) tr(hipHostMalloc(&sc.pinned, kSkPinnedBytes, hipHostMallocDefault));
-  if (e != hipSuccess) return done();
+  if (!tr.ok()) return done();
   unsigned long long* const host = (unsigned long long*)sc.pinned;
-  unsigned long long* const host_word = host + kSkCounterBytes / 8;
+  unsigned long long* const host_word = host + kCounterBytes / 8;
   const SkStream s{(const uint8_t*)blobs, size, blob_off, consider};
 
-  // the count pass: a column of n + 1 counts, the counters, the scan's storage
   {
-    const size_t cc = align256((n + 1) * 8);
-    if (const int rc = sc.reserve(cc + kSkCounterBytes + align256(scan_bytes), stream, herr)) return rc;
-    uint64_t* cnt = (uint64_t*)sc.p;
-    unsigned long long* counter = (unsigned long long*)((uint8_t*)sc.p + cc);
-    void* tmp = (uint8_t*)sc.p + cc + kSkCounterBytes;
-    tr(hipMemsetAsync(cnt + n, 0, 8, stream));
-    tr(hipMemsetAsync(counter, 0, kSkCounterBytes, stream));
-    if (e == hipSuccess) {
-      subkeys_count_kernel<<<(unsigned)nt, kSkBlobs, kWalkLdsBytes, stream>>>(s, n, sk_flags, cnt, counter);
+    auto layout = [&](void* base) {
+      Carver c(base);
+      CountCols k;
+      k.cnt = c.take<uint64_t>(n + 1);
+      k.counter = (unsigned long long*)c.bytes(kCounterBytes);
+      k.tmp = c.bytes(scan_bytes);
+      k.total = c.total();
+      return k;
+    };
+    if (const int rc = sc.reserve(layout(nullptr).total, stream, herr)) return rc;
+    const CountCols k = layout(sc.p);
+    tr(hipMemsetAsync(k.cnt + n, 0, 8, stream));
+    tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
+    if (tr.ok()) {
+      subkeys_count_kernel<<<(unsigned)nt, kSkBlobs, kWalkLdsBytes, stream>>>(s, n, sk_flags, k.cnt, k.counter);
       tr(hipGetLastError());
     }
-    if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, cnt, edge_off, n + 1, stream));
-    if (e == hipSuccess) tr(hipMemcpyAsync(host, counter, kSkCounterBytes, hipMemcpyDeviceToHost, stream));
-    if (e == hipSuccess) tr(hipMemcpyAsync(host_word, edge_off + n, 8, hipMemcpyDeviceToHost, stream));
-    if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
-    if (e == hipSuccess) tr(hipStreamSynchronize(stream));
-    if (e != hipSuccess) return done();
+    if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, scan_bytes, k.cnt, edge_off, n + 1, stream));
+    if (tr.ok()) tr(hipMemcpyAsync(host, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+    if (tr.ok()) tr(hipMemcpyAsync(host_word, edge_off + n, 8, hipMemcpyDeviceToHost, stream));
+    if (tr.ok()) tr(sc.mark_done(stream));
+    if (tr.ok()) tr(hipStreamSynchronize(stream));
+    if (!tr.ok()) return done();
   }
   const uint64_t E = *host_word;
-  counts[0] = sum_word(host, 0);
-  counts[1] = sum_word(host, 1);
-  counts[2] = sum_word(host, 2);
+  counts[0] = counter_sum(host, 0);
+  counts[1] = counter_sum(host, 1);
+  counts[2] = counter_sum(host, 2);
   counts[3] = E;
   counts[4] = 0;
   if (!child) return done();
@@ -386,80 +400,79 @@ int launch_ralledata_subkeys(const void* blobs, uint64_t size, const uint64_t* b
                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, N, 0, sort_bits, stream));
   tr(hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, RalleMaxU32(), N,
                                        stream));
-  if (e != hipSuccess) return done();
-  const size_t c8 = align256(N * 8), c4 = align256(N * 4), cs = align256(N * sizeof(Side)), ct = align256((nt + 1) * 8);
-  const size_t cp = align256(n);
+  if (!tr.ok()) return done();
   size_t tmp_bytes = tile_bytes > sort_bytes ? tile_bytes : sort_bytes;
   if (max_bytes > tmp_bytes) tmp_bytes = max_bytes;
-  if (const int rc = sc.reserve(2 * c8 + 3 * c4 + cs + cp + 2 * ct + kSkCounterBytes + align256(tmp_bytes), stream, herr))
-    return rc;
-  uint8_t* at = (uint8_t*)sc.p;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = at;
-    at += bytes;
-    return p;
+  auto layout = [&](void* base) {
+    Carver c(base);
+    JoinCols k;
+    k.keys_in = c.take<uint64_t>(N);
+    k.keys_out = c.take<uint64_t>(N);
+    k.idx_in = c.take<uint32_t>(N);
+    k.idx_out = c.take<uint32_t>(N);
+    k.bound_s = c.take<uint32_t>(N);
+    k.side = c.take<Side>(N);
+    k.part = c.take<uint8_t>(n);
+    k.tile_count = c.take<uint64_t>(nt + 1);
+    k.tile_base = c.take<uint64_t>(nt + 1);
+    k.counter = (unsigned long long*)c.bytes(kCounterBytes);
+    k.tmp = c.bytes(tmp_bytes);
+    k.total = c.total();
+    return k;
   };
-  uint64_t* keys_in = (uint64_t*)take(c8);
-  uint64_t* keys_out = (uint64_t*)take(c8);  // first the blobs' hashes by index, then the sorted keys
-  uint32_t* idx_in = (uint32_t*)take(c4);
-  uint32_t* idx_out = (uint32_t*)take(c4);
-  uint32_t* bound_s = (uint32_t*)take(c4);
-  Side* side = (Side*)take(cs);
-  uint8_t* part = take(cp);
-  uint64_t* tile_count = (uint64_t*)take(ct);
-  uint64_t* tile_base = (uint64_t*)take(ct);
-  unsigned long long* counter = (unsigned long long*)take(kSkCounterBytes);
-  void* tmp = take(align256(tmp_bytes));
+  if (const int rc = sc.reserve(layout(nullptr).total, stream, herr)) return rc;
+  const JoinCols k = layout(sc.p);
   // free once the sort has read them, its input columns: the first mark column takes the index
   // column's place, its scan and the second mark column the two halves of the key column's
-  uint32_t* mark = idx_in;
-  uint32_t* last_b = (uint32_t*)keys_in;
+  uint32_t* mark = k.idx_in;
+  uint32_t* last_b = (uint32_t*)k.keys_in;
   uint32_t* mark_r = last_b + N;
 
-  tr(hipMemsetAsync(tile_count + nt, 0, 8, stream));
-  tr(hipMemsetAsync(counter, 0, kSkCounterBytes, stream));
-  if (e == hipSuccess) {
-    subkeys_emit_kernel<<<(unsigned)nt, kSkBlobs, kWalkLdsBytes, stream>>>(s, n, edge_off, E, part, keys_out, side,
-                                                                           tile_count, rep);
+  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
+  if (tr.ok()) {
+    subkeys_emit_kernel<<<(unsigned)nt, kSkBlobs, kWalkLdsBytes, stream>>>(s, n, edge_off, E, k.part, k.keys_out,
+                                                                           k.side, k.tile_count, rep);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, tile_bytes, tile_count, tile_base, nt + 1, stream));
-  if (e == hipSuccess) {
-    ralle_compact_kernel<kSkBlobs><<<(unsigned)nt, kSkBlobs, 0, stream>>>(part, keys_out, n, tile_base, nt, E, keys_in,
-                                                                          idx_in);
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tile_bytes, k.tile_count, k.tile_base, nt + 1, stream));
+  if (tr.ok()) {
+    ralle_compact_kernel<kSkBlobs><<<(unsigned)nt, kSkBlobs, 0, stream>>>(k.part, k.keys_out, n, k.tile_base, nt, E,
+                                                                          k.keys_in, k.idx_in);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess && E) {
+  if (tr.ok() && E) {
     subkeys_hash_kernel<<<(unsigned)((E + kSkBlock - 1) / kSkBlock), kSkBlock, 0, stream>>>(
-        s.blobs, n, E, side, tile_base, nt, keys_in, idx_in, make_spad(seed));
+        s.blobs, n, E, k.side, k.tile_base, nt, k.keys_in, k.idx_in, make_spad(seed));
     tr(hipGetLastError());
   }
-  if (e == hipSuccess)
-    tr(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint64_t*)keys_in, keys_out,
-                                          (const uint32_t*)idx_in, idx_out, N, 0, sort_bits, stream));
+  if (tr.ok())
+    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
+                                          (const uint32_t*)k.idx_in, k.idx_out, N, 0, sort_bits, stream));
   const unsigned grid = (unsigned)((N + kSkBlock - 1) / kSkBlock);
-  const uint64_t mask = sort_bits == 64 ? ~0ull : (1ull << sort_bits) - 1;
-  if (e == hipSuccess) {
-    ralle_mark_kernel<kSkBlock><<<grid, kSkBlock, 0, stream>>>(idx_out, N, n, mark);
+  const uint64_t mask = sort_mask(sort_bits);
+  if (tr.ok()) {
+    ralle_mark_kernel<kSkBlock><<<grid, kSkBlock, 0, stream>>>(k.idx_out, N, n, mark);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) {
-    subkeys_bound_kernel<<<grid, kSkBlock, 0, stream>>>(keys_out, idx_out, N, n, mask, mark_r);
+  if (tr.ok()) {
+    subkeys_bound_kernel<<<grid, kSkBlock, 0, stream>>>(k.keys_out, k.idx_out, N, n, mask, mark_r);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess)
-    tr(hipcub::DeviceScan::InclusiveScan(tmp, max_bytes, (const uint32_t*)mark, last_b, RalleMaxU32(), N, stream));
-  if (e == hipSuccess)
-    tr(hipcub::DeviceScan::InclusiveScan(tmp, max_bytes, (const uint32_t*)mark_r, bound_s, RalleMaxU32(), N, stream));
-  if (e == hipSuccess) {
-    subkeys_resolve_kernel<<<grid, kSkBlock, 0, stream>>>(s.blobs, n, keys_out, idx_out, N, mask, last_b, bound_s, side,
-                                                         rep, child, counter);
+  if (tr.ok())
+    tr(hipcub::DeviceScan::InclusiveScan(k.tmp, max_bytes, (const uint32_t*)mark, last_b, RalleMaxU32(), N, stream));
+  if (tr.ok())
+    tr(hipcub::DeviceScan::InclusiveScan(k.tmp, max_bytes, (const uint32_t*)mark_r, k.bound_s, RalleMaxU32(), N,
+                                         stream));
+  if (tr.ok()) {
+    subkeys_resolve_kernel<<<grid, kSkBlock, 0, stream>>>(s.blobs, n, k.keys_out, k.idx_out, N, mask, last_b, k.bound_s,
+                                                         k.side, rep, child, k.counter);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipMemcpyAsync(host, counter, kSkCounterBytes, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
-  if (e == hipSuccess) tr(hipStreamSynchronize(stream));
-  if (e == hipSuccess) counts[4] = sum_word(host, 3);
+  if (tr.ok()) tr(hipMemcpyAsync(host, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(sc.mark_done(stream));
+  if (tr.ok()) tr(hipStreamSynchronize(stream));
+  if (tr.ok()) counts[4] = counter_sum(host, 3);
   return done();
 }
 
@@ -469,67 +482,71 @@ int launch_ralledata_reach(const uint64_t* edge_off, const uint64_t* child, cons
                            const uint8_t* roots, uint64_t max_levels, uint8_t* reach, uint64_t* counts,
                            hipStream_t stream, hipError_t* herr) {
   *herr = hipSuccess;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
+  FirstError tr;
   auto done = [&]() {
-    *herr = e;
-    return e != hipSuccess ? K2H_AMD_EHIP : K2H_AMD_OK;
+    *herr = tr.e;
+    return !tr.ok() ? K2H_AMD_EHIP : K2H_AMD_OK;
   };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
-  if (e != hipSuccess) return done();
-  SkScratch& sc = g_sk[dev];
+  SkScratch* const scp = g_sk.current(tr);
+  if (!tr.ok()) return done();
+  SkScratch& sc = *scp;
   std::lock_guard<std::mutex> lk(sc.mu);
   if (!sc.pinned) tr(hipHostMalloc(&sc.pinned, kSkPinnedBytes, hipHostMallocDefault));
-  if (e != hipSuccess) return done();
+  if (!tr.ok()) return done();
   unsigned long long* const host = (unsigned long long*)sc.pinned;
-  unsigned long long* const host_word = host + kSkCounterBytes / 8;
-  const size_t cb = align256((n + 31) / 32 * 4), c4 = align256(n * 4);
-  if (const int rc = sc.reserve(cb + 2 * c4 + kSkCounterBytes + 256, stream, herr)) return rc;
-  uint32_t* bits = (uint32_t*)sc.p;
-  uint32_t* cur = (uint32_t*)((uint8_t*)sc.p + cb);
-  uint32_t* next = (uint32_t*)((uint8_t*)sc.p + cb + c4);
-  unsigned long long* counter = (unsigned long long*)((uint8_t*)sc.p + cb + 2 * c4);
-  unsigned long long* fcount = counter + kSkCounterBytes / 8;  // the frontier's size, one word per parity of the level
+  unsigned long long* const host_word = host + kCounterBytes / 8;
+  const size_t nbits = (n + 31) / 32;  // bitmap words
+  auto layout = [&](void* base) {
+    Carver c(base);
+    ReachCols k;
+    k.bits = c.take<uint32_t>(nbits);
+    k.cur = c.take<uint32_t>(n);
+    k.next = c.take<uint32_t>(n);
+    k.counter = (unsigned long long*)c.bytes(kCounterBytes + 256);
+    k.total = c.total();
+    return k;
+  };
+  if (const int rc = sc.reserve(layout(nullptr).total, stream, herr)) return rc;
+  const ReachCols k = layout(sc.p);
+  uint32_t *const bits = k.bits, *cur = k.cur, *next = k.next;
+  unsigned long long* const counter = k.counter;
+  unsigned long long* fcount = counter + kCounterBytes / 8;
   const unsigned grid = (unsigned)((n + kSkBlock - 1) / kSkBlock);
-  tr(hipMemsetAsync(bits, 0, cb, stream));
-  tr(hipMemsetAsync(counter, 0, kSkCounterBytes + 256, stream));
-  if (e == hipSuccess) {
+  tr(hipMemsetAsync(bits, 0, align256(nbits * 4), stream));
+  tr(hipMemsetAsync(counter, 0, kCounterBytes + 256, stream));
+  if (tr.ok()) {
     reach_start_kernel<<<grid, kSkBlock, 0, stream>>>(rep, roots, n, bits, cur, fcount);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipMemcpyAsync(host_word, fcount, 8, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipStreamSynchronize(stream));
-  uint64_t fc = e == hipSuccess ? *host_word : 0, levels = 0;
+  if (tr.ok()) tr(hipMemcpyAsync(host_word, fcount, 8, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(hipStreamSynchronize(stream));
+  uint64_t fc = tr.ok() ? *host_word : 0, levels = 0;
   int w = 0;
-  while (e == hipSuccess && fc && (!max_levels || levels < max_levels)) {
+  while (tr.ok() && fc && (!max_levels || levels < max_levels)) {
     w ^= 1;
     tr(hipMemsetAsync(fcount + w, 0, 8, stream));
-    if (e == hipSuccess) {
+    if (tr.ok()) {
       reach_level_kernel<<<(unsigned)((fc + kSkBlock - 1) / kSkBlock), kSkBlock, 0, stream>>>(cur, fc, edge_off, child, n,
                                                                                              bits, next, fcount + w);
       tr(hipGetLastError());
     }
-    if (e == hipSuccess) tr(hipMemcpyAsync(host_word, fcount + w, 8, hipMemcpyDeviceToHost, stream));
-    if (e == hipSuccess) tr(hipStreamSynchronize(stream));
-    if (e == hipSuccess) fc = *host_word;
+    if (tr.ok()) tr(hipMemcpyAsync(host_word, fcount + w, 8, hipMemcpyDeviceToHost, stream));
+    if (tr.ok()) tr(hipStreamSynchronize(stream));
+    if (tr.ok()) fc = *host_word;
     uint32_t* t = cur;
     cur = next;
     next = t;
     ++levels;
   }
-  if (e == hipSuccess) {
+  if (tr.ok()) {
     reach_final_kernel<<<grid, kSkBlock, 0, stream>>>(rep, n, bits, reach, counter);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipMemcpyAsync(host, counter, kSkCounterBytes, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
-  if (e == hipSuccess) tr(hipStreamSynchronize(stream));
-  if (e == hipSuccess) {
-    counts[0] = sum_word(host, 0);
+  if (tr.ok()) tr(hipMemcpyAsync(host, counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(sc.mark_done(stream));
+  if (tr.ok()) tr(hipStreamSynchronize(stream));
+  if (tr.ok()) {
+    counts[0] = counter_sum(host, 0);
     counts[1] = levels;
     counts[2] = fc == 0 ? 1 : 0;
   }

@@ -64,8 +64,6 @@ namespace {
 constexpr int kUlBlobs = 256;        // size / copy: blobs per 256-thread block, one per thread
 constexpr int kUlGroup = 8;          // rewrite: lanes per blob
 constexpr int kUlTabPieces = 4096;   // copy: as kSelTabPieces of the select copy
-constexpr int kUlCounters = 64;      // counts go into this many 64-byte lines, seven words in each
-constexpr size_t kUlCounterBytes = 64 * kUlCounters;
 
 typedef uint32_t u32x2_ua __attribute__((ext_vector_type(2), aligned(1)));
 
@@ -90,7 +88,7 @@ __device__ __forceinline__ void ul_count(unsigned long long* counter, int word, 
   const uint64_t s = wave_sum(v);
   if ((threadIdx.x & 63u) == 0 && s) {
     const uint32_t wave = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    atomicAdd(counter + 8 * (wave % kUlCounters) + word, (unsigned long long)s);
+    atomicAdd(counter + 8 * (wave % kCounterLines) + word, (unsigned long long)s);
   }
 }
 
@@ -328,12 +326,21 @@ __global__ __launch_bounds__(256) void subkeys_drop_mask_kernel(const uint64_t* 
   drop[e] = c == ~0ull ? (uint8_t)dangling : (uint8_t)(gone && c < n && gone[c] != 0);
 }
 
-// The call's temporaries (RalleScratch: one grow-only buffer per device, the next call's stream
-// waits for this call's event) and the pinned lines the counts land in.
-struct UlScratch : RalleScratch {
+// The call's temporaries (k2h_scratch.h) and the pinned lines the counts land in (seven words in
+// each).
+struct UlScratch : DeviceScratch {
   void* pinned = nullptr;
 };
-UlScratch g_ul[64];
+PerDevice<UlScratch> g_ul;
+
+struct UlCols {
+  uint64_t* place;
+  uint32_t* rank;
+  uint8_t* chg;
+  unsigned long long* counter;
+  void* tmp;
+  size_t total;
+};
 
 }  // namespace
 
@@ -345,69 +352,60 @@ int launch_ralledata_unlink(const void* blobs, uint64_t size, const uint64_t* bl
                             const uint8_t* drop, void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* index,
                             uint8_t* changed, uint64_t* counts, hipStream_t stream, hipError_t* herr) {
   *herr = hipSuccess;
-  hipError_t e = hipSuccess;
-  auto tr = [&](hipError_t x) {
-    if (e == hipSuccess) e = x;
-  };
+  FirstError tr;
   auto done = [&](int rc) {
-    *herr = e;
-    return e != hipSuccess ? K2H_AMD_EHIP : rc;
+    *herr = tr.e;
+    return !tr.ok() ? K2H_AMD_EHIP : rc;
   };
-  int dev = 0;
-  tr(hipGetDevice(&dev));
-  if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+  UlScratch* const scp = g_ul.current(tr);
   size_t b8 = 0, b4 = 0;
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b8, (uint64_t*)nullptr, (uint64_t*)nullptr, n + 1, stream));
   tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b4, (uint32_t*)nullptr, (uint32_t*)nullptr, n + 1, stream));
-  if (e != hipSuccess) return done(K2H_AMD_OK);
-  UlScratch& sc = g_ul[dev];
+  if (!tr.ok()) return done(K2H_AMD_OK);
+  UlScratch& sc = *scp;
   std::lock_guard<std::mutex> lk(sc.mu);
-  if (!sc.pinned) tr(hipHostMalloc(&sc.pinned, kUlCounterBytes, hipHostMallocDefault));
-  if (e != hipSuccess) return done(K2H_AMD_OK);
+  if (!sc.pinned) tr(hipHostMalloc(&sc.pinned, kCounterBytes, hipHostMallocDefault));
+  if (!tr.ok()) return done(K2H_AMD_OK);
   unsigned long long* const host = (unsigned long long*)sc.pinned;
-  const size_t c8 = align256((n + 1) * 8), c4 = align256((n + 1) * 4), c1 = align256(n);
-  if (const int rc = sc.reserve(c8 + c4 + c1 + kUlCounterBytes + align256(b8 > b4 ? b8 : b4), stream, herr)) return rc;
-  uint8_t* at = (uint8_t*)sc.p;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = at;
-    at += bytes;
-    return p;
+  auto layout = [&](void* base) {
+    Carver c(base);
+    UlCols k;
+    k.place = c.take<uint64_t>(n + 1);
+    k.rank = c.take<uint32_t>(n + 1);
+    k.chg = c.take<uint8_t>(n);
+    k.counter = (unsigned long long*)c.bytes(kCounterBytes);
+    k.tmp = c.bytes(b8 > b4 ? b8 : b4);
+    k.total = c.total();
+    return k;
   };
-  uint64_t* place = (uint64_t*)take(c8);
-  uint32_t* rank = (uint32_t*)take(c4);
-  uint8_t* chg = take(c1);
-  unsigned long long* counter = (unsigned long long*)take(kUlCounterBytes);
-  void* tmp = at;
+  if (const int rc = sc.reserve(layout(nullptr).total, stream, herr)) return rc;
+  const UlCols k = layout(sc.p);
   const UlIn s{(const uint8_t*)blobs, size, blob_off, keep, sk_flags, edge_off, drop};
 
-  tr(hipMemsetAsync(counter, 0, kUlCounterBytes, stream));
-  if (e == hipSuccess) {
-    unlink_size_kernel<<<(unsigned)(n / kUlBlobs + 1), kUlBlobs, drop ? kWalkLdsBytes : 0, stream>>>(s, n, place, rank, chg,
-                                                                                                    changed, counter);
+  tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
+  if (tr.ok()) {
+    unlink_size_kernel<<<(unsigned)(n / kUlBlobs + 1), kUlBlobs, drop ? kWalkLdsBytes : 0, stream>>>(
+        s, n, k.place, k.rank, k.chg, changed, k.counter);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, b8, place, place, n + 1, stream));
-  if (e == hipSuccess) tr(hipcub::DeviceScan::ExclusiveSum(tmp, b4, rank, rank, n + 1, stream));
-  if (e == hipSuccess) tr(hipMemcpyAsync(host, counter, kUlCounterBytes, hipMemcpyDeviceToHost, stream));
-  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
-  if (e == hipSuccess) tr(hipStreamSynchronize(stream));
-  if (e != hipSuccess) return done(K2H_AMD_OK);
-  for (int k = 0; k < 7; ++k) {
-    uint64_t sum = 0;
-    for (int c = 0; c < kUlCounters; ++c) sum += host[8 * c + k];
-    counts[k] = sum;
-  }
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b8, k.place, k.place, n + 1, stream));
+  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b4, k.rank, k.rank, n + 1, stream));
+  if (tr.ok()) tr(hipMemcpyAsync(host, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
+  if (tr.ok()) tr(sc.mark_done(stream));
+  if (tr.ok()) tr(hipStreamSynchronize(stream));
+  if (!tr.ok()) return done(K2H_AMD_OK);
+  for (int w = 0; w < 7; ++w) counts[w] = counter_sum(host, w);
   if (!out) return done(K2H_AMD_OK);
   if (counts[1] > out_cap) return done(K2H_AMD_EINVAL);
   unlink_copy_kernel<<<(unsigned)((n + kUlBlobs - 1) / kUlBlobs), kUlBlobs, 0, stream>>>(
-      s.blobs, blob_off, n, place, rank, chg, (uint8_t*)out, out_off, index);
+      s.blobs, blob_off, n, k.place, k.rank, k.chg, (uint8_t*)out, out_off, index);
   tr(hipGetLastError());
-  if (e == hipSuccess && counts[2]) {
+  if (tr.ok() && counts[2]) {
     const uint64_t per = 256 / kUlGroup;
-    unlink_rewrite_kernel<<<(unsigned)((n + per - 1) / per), 256, 0, stream>>>(s, n, place, chg, (uint8_t*)out);
+    unlink_rewrite_kernel<<<(unsigned)((n + per - 1) / per), 256, 0, stream>>>(s, n, k.place, k.chg, (uint8_t*)out);
     tr(hipGetLastError());
   }
-  if (e == hipSuccess) tr(hipEventRecord(sc.done, stream));
+  if (tr.ok()) tr(sc.mark_done(stream));
   return done(K2H_AMD_OK);
 }
 
