@@ -1060,7 +1060,7 @@ int k2h_amd_archive_scan_prehash_device(const void* file, uint64_t size, k2h_amd
  * attrs segments are ones K2HSubKeys / K2HAttrs::Serialize accept, as the library's writer
  * produces them.  Parity with Load is a restatement: libk2hash itself is not built by this
  * project's tests (it needs libfullock).  Merging a key's surviving records into one SET_ALL
- * is not done.
+ * is not done (here: section 5c does it, k2h_amd_archive_apply with an empty held stream).
  *
  *   h1       (n entries, may be NULL) k2h_hash of each key, as k2h_amd_archive_prehash gives it.
  *            Only a grouping key: identity is always decided on key length and key bytes, and
@@ -1094,6 +1094,112 @@ int k2h_amd_archive_scan_prehash_device(const void* file, uint64_t size, k2h_amd
  * memory: about 72 bytes per record plus the sort's own, kept per device between calls. */
 int k2h_amd_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
                          const uint64_t* h1, uint8_t* keep, uint64_t* by, uint64_t* dropped, void* stream);
+
+/* 5c. A transaction log applied to a held RALLEDATA stream: replication on the device.  A peer
+ * holds yesterday's elements as a blob stream (section 4) and receives the log; the call gives
+ * the stream that holds the new state.  It is also the merge section 5b leaves undone -- with an
+ * empty held stream (na = 0) the output is one blob per surviving key, so a log with REPLACE_*
+ * and DEL_KEY records becomes a snapshot, which k2h_amd_archive_ralledata (SET_ALL only) cannot
+ * give.  All pointers are device pointers except counts and stop.
+ *
+ * Stop.  *stop is the index of the first record with consider[i] != 0, status == 0 and type
+ * OW_VAL or RENAME; n when there is none.  Such a record with a bad status or consider[i] == 0
+ * does not count.  Only the prefix [0, stop) is the log for everything below: records at or
+ * behind stop are not applied and leave no trace.  OW_VAL and RENAME are not executed on the
+ * device; the caller handles that one record itself and calls again with the rest of the log
+ * and this call's output as the held stream.
+ *
+ * Participants.  Record i takes part by the rule of 5b (status 0, type 0..6, key_len >= 1, key
+ * range inside [0, size), checked on the device) and also needs consider[i] != 0 and i < stop.
+ * Held blob j takes part by the rule of 4b''''' (a span inside [0, held_size) of at least 80
+ * bytes; header not EMPTY, NO_KEY or BAD_RANGE) and also needs held_keep[j] != 0.  A held blob
+ * with held_keep[j] == 0 or a bad span is not emitted at all; one with a good span that is kept
+ * but takes no part is copied through unchanged.
+ *
+ * Identity is (hash, subhash, key length, key bytes).  A blob uses its stored fields, trusted
+ * as in _dedup and _diff; a record uses h1[i] and h2[i].  With h1 == h2 == NULL the call
+ * computes both by the prehash path (k2h_amd_archive_prehash; flags: K2H_AMD_FLAG_STD_FNV or 0,
+ * and 0 when the hashes are given).  Unlike 5b's h1 these values are no mere grouping key: they
+ * end up in the output headers and must be those of the table's hash function.  A held blob
+ * whose stored hashes are not those of its key is never matched, as Load would never find it.
+ *
+ * The rule.  Per identity the prior element is the (V, S, A) of the LAST held participant of
+ * that identity; earlier held copies of an identity, touched by a record or not, are left out
+ * of the output and counted as superseded.  The final element is what Load's switch
+ * (lib/k2harchive.cc:328-341) leaves after the identity's participant records in log order,
+ * under the preconditions of 5b.  In last-writer terms: walk the identity's records from the
+ * last one backwards.  A DEL_KEY ends the walk with every field still open empty, and with the
+ * element absent when no later record wrote.  SET_ALL supplies V always, S and A only when its
+ * own are non-empty; REPLACE_* supplies its one field, empty data clears it.  Fields still open
+ * at the start come from the prior element.  An identity with an applied record whose last one
+ * is no DEL_KEY exists, even with all three fields empty.  A record's data segment whose range
+ * is not inside [0, size) is taken as empty.
+ *
+ * Output.  Two parts, back to back; out_off has counts[0] + 1 entries and starts at 0.
+ *   part 1  in held order: every kept, good-span held blob that takes no part, and the deciding
+ *           blob of every identity that no applied record touches; byte for byte, slack
+ *           included.  It equals k2h_amd_ralledata_select of the held stream under
+ *           keep[j] = (touched[j] == 0).
+ *   part 2  one blob per touched identity whose final element exists, in the order of the
+ *           identities' last applied records, each in GetElementToBinary's layout
+ *           (lib/k2hshmdirect.cc:59-89): the identity's hash and subhash; key_pos = 80 and the
+ *           running sums, written for zero-length segments too; length exactly 80 plus the four
+ *           lengths.  Segment bytes are read from wherever their source puts them: a record's
+ *           file ranges, or a held blob's permuted, gapped or overlapping segments.  Part 2 on
+ *           its own is the incremental dump.  A part-2 blob with a key and nothing else leaves
+ *           no element when fed (SetElementByBinArray, lib/k2hshmdirect.cc:438), where Load
+ *           leaves an element with a key and no value (as in 4b''''''').
+ *
+ *   origin[k]   (counts[0] entries, may be NULL) j for a part-1 blob; na + i for a part-2 blob,
+ *               i the identity's last applied record
+ *   touched[j]  (na entries, may be NULL) 0: emitted unchanged; K2H_AMD_APPLY_TOUCHED: the
+ *               deciding blob of an identity with applied records -- whatever is left of it is
+ *               in part 2; K2H_AMD_APPLY_SUPERSEDED: an earlier copy; K2H_AMD_APPLY_LEFT_OUT:
+ *               not kept, or a bad span
+ *   counts      (host, 7 entries, required) blobs emitted; bytes emitted; part-1 blobs; held
+ *               blobs touched; held blobs superseded; touched identities left absent; records
+ *               applied
+ *   stop        (host, required)
+ *
+ * `stream` is synchronised exactly once per call, to return counts and stop (never when
+ * na == 0 and n == 0).  out == NULL: count only -- counts, stop and, if given, touched are filled.
+ * counts[1] > out_cap: K2H_AMD_EINVAL with counts, stop and touched set and nothing written to
+ * out, out_off or origin.  K2H_AMD_EINVAL, judged on the host before any device is touched, each
+ * with its own message: counts or stop NULL; held or held_off NULL with na > 0; file or recs
+ * NULL with n > 0; out given without out_off; exactly one of h1 / h2 NULL; flags other than
+ * K2H_AMD_FLAG_STD_FNV, or any flag with the hashes given; na + n > 2^32 - 2.
+ * na == 0 && n == 0: K2H_AMD_OK, counts and stop zeroed, out_off[0] = 0 when out_off is given.
+ * n == 0, or stop == 0: the call is _select of the held stream without its superseded copies.
+ *
+ * A consider mask from k2h_amd_archive_fold is valid only if the fold saw exactly the records
+ * [0, stop): it drops a record because of LATER records of its key, which may lie behind the
+ * stop.  Without a mask the result is the same -- the fold never drops a key's last record, so
+ * the anchors do not move -- but a key with r applied records then costs a backward walk of up
+ * to r steps in one lane (the walk ends as soon as V, S and A are covered, so a long run of
+ * SET_ALLs is cheap and a head REPLACE_SKEY before a long run of REPLACE_VALs is not).  r
+ * DISTINCT identities that share the sorted hash bits cost O(r) steps per lane (wrong or
+ * crafted hashes only, the case 4b'''' documents).
+ *
+ * Memory rule as in 5b and 4b''''': no byte outside [0, held_size) of the held stream or
+ * [0, size) of the file is read, except within the aligned 16 bytes that hold a valid byte;
+ * all absolute offsets are 64-bit.  Temporary device memory, kept per device between calls:
+ * about 69 bytes per held blob and record, 16 more per record and 16 more when the call hashes
+ * the keys, plus the sort's own. */
+#define K2H_AMD_APPLY_TOUCHED 1u
+#define K2H_AMD_APPLY_SUPERSEDED 2u
+#define K2H_AMD_APPLY_LEFT_OUT 3u
+
+int k2h_amd_archive_apply(const void* held, uint64_t held_size, const uint64_t* held_off, uint64_t na,
+                          const uint8_t* held_keep, /* na, or NULL: every blob; _select's meaning */
+                          const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
+                          const uint8_t* consider,  /* n, or NULL: every record */
+                          const uint64_t* h1, const uint64_t* h2, /* n each, both or neither */
+                          uint32_t flags,           /* K2H_AMD_FLAG_STD_FNV, only when h1 / h2 are NULL */
+                          void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* origin,
+                          uint8_t* touched,         /* na, may be NULL */
+                          uint64_t* counts,         /* host, 7 entries, required */
+                          uint64_t* stop,           /* host, required */
+                          void* stream);
 
 /* k2himport inputs (tests/k2himport.cc:74-117): k2h_amd_import_scan splits a TSV
  * (key TAB value NEWLINE) or mdbm_export file (five header lines ending "HEADER=END",

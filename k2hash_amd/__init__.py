@@ -19,12 +19,15 @@ and (2) a batch C ABI backed by hand-written gfx950 HIP kernels (section 2).
              blobs (drop_mask, unlink_subkeys, prune_ralledata; also reachable through subkeys)
   archive    k2hash archives scanned and prehashed on the GPU, and transaction logs folded to
              the records that still matter under Load's rule (fold_device, compact_device)
+  apply      a transaction log applied to a held blob stream: replication, and log -> snapshot
+             (apply_log, apply_records)
   shard      multi-GPU partitioning and the RCCL gather of hashes
 """
 from .hashfunc import (K2H_2ND_HASH_FUNC, K2H_HASH_FUNC, K2H_HASH_VER_FUNC, K2HashDynLib, k2h_hash,
                        k2h_hash_version, k2h_second_hash)
 from .batch import (bucket_index, hash_csr, hash_csr_host, hash_csr_index, hash_fixed, hash_fixed_host,
                     hash_fixed_index, synth_bytes, synth_offsets, unpack_kindex, version)
+from .apply import Applied, apply_log, apply_records
 from .archive import compact_device, fold_device
 from .ralledata import (Diff, HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
                         dedup_ralledata, diff_ralledata, import_file_to_archive, import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
@@ -41,5 +44,5 @@ __all__ = [
     "dedup_ralledata", "partition_ralledata", "ralledata_to_archive", "import_file_to_archive",
     "blob_times", "TimeWindow", "Times", "fold_device", "compact_device", "diff_ralledata", "Diff",
     "subkey_edges", "reach_subkeys", "subtree_ralledata", "SubkeyEdges", "Reach",
-    "drop_mask", "unlink_subkeys", "prune_ralledata", "Unlinked",
+    "drop_mask", "unlink_subkeys", "prune_ralledata", "Unlinked", "apply_log", "apply_records", "Applied",
 ]

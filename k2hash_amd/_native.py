@@ -85,6 +85,7 @@ K2H_AMD_DIFF_ATTRS, K2H_AMD_DIFF_DATA, K2H_AMD_DIFF_REPEAT, K2H_AMD_DIFF_APPLY =
 
 K2H_AMD_SKEY_PART, K2H_AMD_SKEY_HAS, K2H_AMD_SKEY_BAD = 0x1, 0x2, 0x4
 K2H_AMD_UNLINK_REWRITTEN, K2H_AMD_UNLINK_EMPTIED, K2H_AMD_UNLINK_KEY_ONLY = 0x1, 0x2, 0x4
+K2H_AMD_APPLY_TOUCHED, K2H_AMD_APPLY_SUPERSEDED, K2H_AMD_APPLY_LEFT_OUT = 1, 2, 3
 
 _twp = ctypes.POINTER(TimeWindowStruct)
 _dtp = ctypes.POINTER(DiffTimes)
@@ -134,6 +135,8 @@ SIGNATURES = {
     "k2h_amd_archive_scan_prehash_device": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p,
                                                            ctypes.c_uint32, _p]),
     "k2h_amd_archive_fold": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _p]),
+    "k2h_amd_archive_apply": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _p, _p, _p, ctypes.c_uint32,
+                                             _p, _u64, _p, _p, _p, _u64p, _u64p, _p]),
     "k2h_amd_import_scan": (ctypes.c_int, [_p, _u64, ctypes.c_int, _p, _u64, _p]),
     "k2h_amd_import_prehash_host": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, ctypes.c_uint32, ctypes.c_int]),
     "k2h_amd_import_scan_device": (ctypes.c_int, [_p, _u64, ctypes.c_int, _p, _u64, _p, _p]),

@@ -698,6 +698,45 @@ __attribute__((visibility("default"))) int k2h_amd_archive_fold(const void* file
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_archive_fold", e);
 }
 
+// Section 5c: a log applied to a held blob stream.  Judged on the host like the one above.
+__attribute__((visibility("default"))) int k2h_amd_archive_apply(
+    const void* held, uint64_t held_size, const uint64_t* held_off, uint64_t na, const uint8_t* held_keep,
+    const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n, const uint8_t* consider,
+    const uint64_t* h1, const uint64_t* h2, uint32_t flags, void* out, uint64_t out_cap, uint64_t* out_off,
+    uint64_t* origin, uint8_t* touched, uint64_t* counts, uint64_t* stop, void* stream) {
+  if (!counts) return fail(K2H_AMD_EINVAL, "archive_apply: NULL counts");
+  if (!stop) return fail(K2H_AMD_EINVAL, "archive_apply: NULL stop");
+  for (int k = 0; k < 7; ++k) counts[k] = 0;
+  *stop = n;
+  if (na && !held) return fail(K2H_AMD_EINVAL, "archive_apply: NULL held");
+  if (na && !held_off) return fail(K2H_AMD_EINVAL, "archive_apply: NULL held_off");
+  if (n && !file) return fail(K2H_AMD_EINVAL, "archive_apply: NULL file");
+  if (n && !recs) return fail(K2H_AMD_EINVAL, "archive_apply: NULL recs");
+  if (out && !out_off) return fail(K2H_AMD_EINVAL, "archive_apply: out given without out_off");
+  if (!h1 != !h2) return fail(K2H_AMD_EINVAL, "archive_apply: h1 and h2 are given together or not at all");
+  if (flags & ~K2H_AMD_FLAG_STD_FNV) return fail(K2H_AMD_EINVAL, "archive_apply: unknown flags");
+  if (flags && h1) return fail(K2H_AMD_EINVAL, "archive_apply: flags choose the hash only when h1 and h2 are NULL");
+  if (na > 0xFFFFFFFEull || n > 0xFFFFFFFEull - na)
+    return fail(K2H_AMD_EINVAL, "archive_apply: more than 2^32 - 2 blobs and records (indices are sorted as 32-bit values)");
+  if (na + n == 0 && !out_off) return K2H_AMD_OK;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  if (na + n == 0) {  // nothing held, no log: out_off[0] = 0
+    e = hipMemsetAsync(out_off, 0, 8, (hipStream_t)stream);
+    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "archive_apply: hipMemsetAsync", e);
+  }
+  int rc = k2h::launch_archive_apply(held, held_size, held_off, na, held_keep, file, size, recs, n, consider, h1, h2,
+                                     seed_for(flags), out, out_cap, out_off, origin, touched, counts, stop,
+                                     (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EINVAL) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "archive_apply: the %llu bytes of the emitted blobs exceed out_cap %llu",
+             (unsigned long long)counts[1], (unsigned long long)out_cap);
+    return fail(rc, msg);
+  }
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_archive_apply", e);
+}
+
 // ---------------------------------------------------------------------------
 // RALLEDATA producer (include/k2hash_amd.h section 4)
 // ---------------------------------------------------------------------------

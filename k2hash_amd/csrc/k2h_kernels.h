@@ -240,6 +240,16 @@ int launch_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_r
                         const uint64_t* h1, uint64_t seed, uint8_t* keep, uint64_t* by, uint64_t* dropped,
                         hipStream_t stream, hipError_t* herr);
 
+// A log applied to a held blob stream (k2h_archive_apply.hip).  Returns a K2H_AMD_* code (the HIP
+// error in *herr) and synchronises the stream once.  1 <= na + n <= 2^32 - 2; h1 and h2 both
+// given or both NULL (then hashed with `seed`).  K2H_AMD_EINVAL: out != NULL and counts[1] >
+// out_cap (counts, stop and touched are filled).
+int launch_archive_apply(const void* held, uint64_t held_size, const uint64_t* held_off, uint64_t na,
+                         const uint8_t* held_keep, const void* file, uint64_t size, const k2h_amd_archive_rec* recs,
+                         uint64_t n, const uint8_t* consider, const uint64_t* h1, const uint64_t* h2, uint64_t seed,
+                         void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* origin, uint8_t* touched,
+                         uint64_t* counts, uint64_t* stop, hipStream_t stream, hipError_t* herr);
+
 // S_p = seed * P^-p (p = 0..15): start states for end-aligned chunking (k2h_csr.hip).
 struct SpadTable {
   uint64_t v[16];

@@ -20,9 +20,9 @@
 //            read and the kernel runs at full occupancy.
 //   scan     two exclusive sums: the sizes into places, the kept flags into ranks.  The counts
 //            come back to the host (the one synchronisation).
-//   copy     the select copy kernel's scheme over the places: a tile of 256 blobs writes its
-//            destination span as aligned 16-byte pieces, one unaligned load each where the
-//            source is contiguous.  A rewritten blob supplies no byte here: a piece wholly
+//   copy     the select copy kernel's scheme over the places (k2h_ralle_copy.h): a tile of
+//            256 blobs writes its destination span as aligned 16-byte pieces, one unaligned
+//            load each where the source is contiguous.  A rewritten blob supplies no byte here: a piece wholly
 //            inside one is skipped, a piece it shares with its neighbours is stored with
 //            filler in the rewritten blob's places.
 //   rewrite  launched only when a blob is rewritten, after the copy on the same stream, so its
@@ -55,6 +55,7 @@
 #include "k2h_kernels.h"
 #include "k2h_ralle_header.h"
 #include "k2h_ralle_ident.h"
+#include "k2h_ralle_copy.h"
 #include "k2h_ralle_pieces.h"
 #include "k2h_ralle_subkeys.h"
 
@@ -154,113 +155,6 @@ __global__ __launch_bounds__(kUlBlobs) void unlink_size_kernel(UlIn s, uint64_t 
   ul_count(counter, 4, (ch & K2H_AMD_UNLINK_EMPTIED) ? 1 : 0);
   ul_count(counter, 5, (ch & K2H_AMD_UNLINK_KEY_ONLY) ? 1 : 0);
   ul_count(counter, 6, mismatch ? 1 : 0);
-}
-
-// The select copy kernel (k2h_ralledata_check.hip) over scanned places: the tile's emitted blobs
-// land back to back at out + place[first blob of the tile]; blob j of the tile holds span bytes
-// [pre[j], pre[j + 1]); an unchanged blob's span byte x sits at blobs[x + delta[j]].  A rewritten
-// blob (rw[j]) has its span in the output and no source here: the rewrite kernel, which runs
-// after this one, writes it.  Pieces wholly inside it are skipped; a piece it shares with other
-// blobs is gathered and stored whole, with the rewritten blob's first source byte as filler.
-__global__ __launch_bounds__(kUlBlobs) void unlink_copy_kernel(const uint8_t* __restrict__ blobs,
-                                                               const uint64_t* __restrict__ off, uint64_t n,
-                                                               const uint64_t* __restrict__ place,
-                                                               const uint32_t* __restrict__ rank,
-                                                               const uint8_t* __restrict__ chg, uint8_t* __restrict__ out,
-                                                               uint64_t* __restrict__ out_off,
-                                                               uint64_t* __restrict__ index) {
-  typedef uint32_t u32x4_al __attribute__((ext_vector_type(4)));
-  __shared__ uint64_t pre[kUlBlobs + 1];
-  __shared__ uint64_t delta[kUlBlobs];
-  __shared__ uint8_t rw[kUlBlobs];
-  __shared__ uint8_t tab[kUlTabPieces];
-  const uint32_t tid = threadIdx.x;
-  const uint64_t r0 = (uint64_t)blockIdx.x * kUlBlobs, i = r0 + tid;
-  const uint64_t D0 = place[r0];
-  const uint64_t B = place[n - r0 < (uint64_t)kUlBlobs ? n : r0 + kUlBlobs] - D0;
-  uint64_t x = B, len = 0, b = 0;
-  uint32_t rewritten = 0;
-  if (i < n) {
-    const uint64_t at = place[i];
-    const uint32_t rk = rank[i];
-    x = at - D0;
-    len = place[i + 1] - at;
-    if (rank[i + 1] != rk) {
-      b = off[i];
-      rewritten = chg[i] & K2H_AMD_UNLINK_REWRITTEN;
-      out_off[rk] = at;
-      if (index) index[rk] = i;
-    }
-  }
-  pre[tid] = x;
-  delta[tid] = b - x;
-  rw[tid] = (uint8_t)rewritten;
-  if (tid == 0) pre[kUlBlobs] = B;
-  if (blockIdx.x == 0 && tid == 0) out_off[rank[n]] = place[n];
-  uint8_t* const dst = out + D0;
-  const uint32_t a = (uint32_t)((uintptr_t)dst & 15u);
-  const uint64_t npieces = (a + B + 15) >> 4;
-  const bool tabled = npieces <= (uint64_t)kUlTabPieces;  // block-uniform
-  if (tabled && len) {
-    const uint32_t last = (uint32_t)((x + len - 1 + a) >> 4);
-    for (uint32_t p = x ? (uint32_t)((x + a + 15) >> 4) : 0u; p <= last; ++p) tab[p] = (uint8_t)tid;
-  }
-  __syncthreads();
-  if (!B) return;
-  for (uint64_t p = tid; p < npieces; p += kUlBlobs) {
-    // the piece holds span bytes [x0, x0 + 16), this tile's part of it [xl, xh)
-    const int64_t x0 = (int64_t)(16 * p) - (int64_t)a;
-    const uint64_t xl = x0 < 0 ? 0 : (uint64_t)x0, xh = (uint64_t)(x0 + 16) < B ? (uint64_t)(x0 + 16) : B;
-    uint32_t j = 0;  // the blob holding byte xl: the last j with pre[j] <= xl
-    if (tabled) {
-      j = tab[p];
-    } else {
-#pragma unroll
-      for (uint32_t step = kUlBlobs / 2; step; step >>= 1)
-        if (pre[j + step] <= xl) j += step;
-    }
-    if (rw[j] && pre[j + 1] >= xh) continue;  // wholly the rewrite kernel's
-    const bool whole = xh - xl == 16;
-    bool contiguous = whole && !rw[j];
-    if (contiguous && pre[j + 1] < xh) {  // past blob j: every blob up to the one holding xh - 1
-      for (uint32_t m = j; pre[m + 1] < xh;) {
-        ++m;
-        if (pre[m + 1] > pre[m] && (rw[m] || delta[m] != delta[j])) contiguous = false;
-      }
-    }
-    if (contiguous) {
-      const u32x4_ua w = *reinterpret_cast<const u32x4_ua*>(blobs + xl + delta[j]);
-      *reinterpret_cast<u32x4_al*>(dst + x0) = u32x4_al{w.x, w.y, w.z, w.w};
-      continue;
-    }
-    // eight places at a time, as the select copy: every place's source address, then the loads
-    uint32_t w[4];
-    uint32_t m = j;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const uint8_t* src[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int64_t y = x0 + 8 * h + k;
-        const uint64_t yc = y < (int64_t)xl ? xl : y >= (int64_t)xh ? xh - 1 : (uint64_t)y;
-        while (pre[m + 1] <= yc) ++m;
-        src[k] = blobs + (rw[m] ? pre[m] : yc) + delta[m];
-      }
-      uint32_t bt[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) bt[k] = *src[k];
-      w[2 * h] = bt[0] | bt[1] << 8 | bt[2] << 16 | bt[3] << 24;
-      w[2 * h + 1] = bt[4] | bt[5] << 8 | bt[6] << 16 | bt[7] << 24;
-    }
-    if (whole) {
-      *reinterpret_cast<u32x4_al*>(dst + x0) = u32x4_al{w[0], w[1], w[2], w[3]};
-    } else {
-      for (uint64_t y = xl; y < xh; ++y) {
-        const uint32_t k = (uint32_t)((int64_t)y - x0);
-        dst[y] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-      }
-    }
-  }
 }
 
 // One rewritten blob by a group of kUlGroup lanes, in GetElementToBinary's layout.  The size
@@ -397,7 +291,8 @@ int launch_ralledata_unlink(const void* blobs, uint64_t size, const uint64_t* bl
   for (int w = 0; w < 7; ++w) counts[w] = counter_sum(host, w);
   if (!out) return done(K2H_AMD_OK);
   if (counts[1] > out_cap) return done(K2H_AMD_EINVAL);
-  unlink_copy_kernel<<<(unsigned)((n + kUlBlobs - 1) / kUlBlobs), kUlBlobs, 0, stream>>>(
+  ralle_place_copy_kernel<true, kUlBlobs, kUlTabPieces>
+      <<<(unsigned)((n + kUlBlobs - 1) / kUlBlobs), kUlBlobs, 0, stream>>>(
       s.blobs, blob_off, n, k.place, k.rank, k.chg, (uint8_t*)out, out_off, index);
   tr(hipGetLastError());
   if (tr.ok() && counts[2]) {
