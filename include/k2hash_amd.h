@@ -524,7 +524,8 @@ int k2h_amd_ralledata_dedup_mtime(const void* blobs, uint64_t size, const uint64
  *                   section 4b''''.
  *   seen[j]  (nb entries, may be NULL) 1 when some participant of A has match == j, else 0; all
  *            nb entries are written.  The blobs of B with seen 0 are the held elements A does
- *            not mention.  Removing them is not done here or anywhere: seen only reports them.
+ *            not mention.  This call only reports them; k2h_amd_ralledata_delta (section 4d')
+ *            turns them into DEL_KEY records.
  *   counts   (host, 4 entries, may be NULL) participants of A, FOUND, FOUND with no differ bit,
  *            APPLY.  counts != NULL: `stream` is synchronised once; else the call is
  *            asynchronous.
@@ -932,6 +933,97 @@ int k2h_amd_archive_ralledata(const void* file, uint64_t size, const struct k2h_
 int k2h_amd_ralledata_archive(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
                               const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* rec_off,
                               uint64_t* records, uint64_t* total, void* stream);
+
+/* 4d'. From two dumps to a log: the transaction log that turns a held stream into a new one.
+ * The calls of section 5 read a K2HTransaction log in every useful way; this one writes it.  A is
+ * the new stream (today's dump), B the held one (yesterday's); rel (na entries) and seen (nb
+ * entries) are the outputs of k2h_amd_ralledata_diff over the same two streams and consider
+ * masks, called without `times`.  The records are what K2HArchive::Load replays onto
+ * yesterday's table to get today's, and what k2h_amd_archive_apply (section 5c) replays onto
+ * yesterday's stream: the call is the inverse of that one.  All pointers are device pointers,
+ * except counts.
+ *
+ * Slots.  A blob i is slot i, B blob j is slot na + j.  Every slot yields 0 to 3 records, back
+ * to back in out[slot_off[s], slot_off[s+1]); slot_off has na + nb + 1 entries, slot_off[0] = 0.
+ *   A slot without K2H_AMD_DIFF_PART   nothing.
+ *   A slot with PART, without FOUND    one SET_ALL with the blob's key and its value, subkeys and
+ *                                      attrs, as section 4d writes it; a key-only blob gives a
+ *                                      key-only SET_ALL.
+ *   A slot with PART and FOUND         one record per differ bit, in the order _VAL, _SKEY,
+ *                                      _ATTRS: REPLACE_VAL(key, value), REPLACE_SKEY(key, subkeys),
+ *                                      REPLACE_ATTRS(key, attrs), each with the A blob's current
+ *                                      bytes of that field, which may be empty: Load clears the
+ *                                      field then, which a SET_ALL cannot (K2HShm::ReplaceAll
+ *                                      writes subkeys and attrs only when the record's own are
+ *                                      non-empty, lib/k2hshm.cc:2948-2950).  No differ bit: nothing.
+ *   B slot j                           one DEL_KEY(key) when seen[j] == 0 and b_consider is NULL
+ *                                      or b_consider[j] != 0.
+ * seen == NULL means no deletions: nothing of B is read, and b_blobs / b_off may be NULL.
+ * _REPEAT, _APPLY and _DATA are ignored.
+ *
+ * The rule is right when each stream has one participant per identity, as a dump has: two
+ * new-key copies in A would give two SET_ALLs of which the second cannot clear what the first
+ * set, and an earlier copy in B has seen == 0 and would delete a key A still has.  A caller whose
+ * streams may repeat an identity reduces each to the last copy first and passes that as the
+ * consider masks of the diff and as b_consider here (INTEGRATION.md 2c''').
+ *
+ * Record bytes: exactly what K2HCommandArchive::Put writes for the type (lib/k2hcommand.cc:69-135,
+ * scom_init at lib/k2hcommand.h:99-113).  The header is packed and 104 bytes long: szCommand
+ * "\nK2H_SET_ALL", "\nK2H_REP_VAL", "\nK2H_REP_SKEY", "\nK2H_REP_ATTRS" or "\nK2H_DEL_KEY",
+ * NUL-padded to 16; the type; the five lengths, 0 for what the type does not carry; key_pos = 104,
+ * the carried segment's position right behind the key (SET_ALL: the three behind each other), and
+ * 104 for every position the type does not carry, exdata_pos included.  The key and the carried
+ * bytes follow.
+ *
+ * Memory safety does not rest on rel or seen.  The writer judges every blob it is about to read
+ * again: its span lies inside [0, size) and has at least 80 bytes, and its header passes the
+ * header tests of k2h_amd_ralledata_check (not EMPTY, NO_KEY or BAD_RANGE).  A slot whose bits
+ * ask for a record but whose blob fails that test yields nothing and is counted as refused.
+ * Segments are read at their *_pos wherever they lie inside the blob; the pos of a length-0
+ * segment is ignored.
+ *
+ *   made[s]  (na + nb entries, may be NULL) a bit per record the slot yielded, K2H_AMD_DELTA_*.
+ *   counts   (host, 8 entries, required) records, bytes, then the records per type -- SET_ALL,
+ *            REPLACE_VAL, REPLACE_SKEY, REPLACE_ATTRS, DEL_KEY -- and the refused slots.
+ *
+ * Flow, the convention of section 4d: a sizing pass and two exclusive sums, `stream` is
+ * synchronised once to return counts, then the records are built asynchronously on `stream`.
+ * out == NULL: sizes, made and counts only (slot_off may then be NULL too).  counts[1] >
+ * out_cap: K2H_AMD_EINVAL with counts, slot_off and made set and nothing written to out.
+ * na + nb == 0: K2H_AMD_OK, counts zeroed, slot_off[0] = 0 if slot_off is given.
+ *
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ * counts NULL; rel NULL with na > 0; A's blobs or offsets NULL with na > 0; B's blobs or offsets
+ * NULL with nb > 0 and seen given; slot_off NULL with out given and na + nb > 0; na + nb >
+ * 2^32 - 2 (the emitting slots are ranked in 32 bits, and no launch grid would fit).
+ *
+ * No byte outside [0, size) of either stream is read except within the aligned 16 bytes that
+ * hold a valid byte; nothing of a slot that asks for no record, nothing of a blob whose span is
+ * bad, and nothing beyond the header of any other blob that is refused.  Nothing outside
+ * out[0, counts[1]), slot_off[0 .. na + nb] and made[0, na + nb) is written; bytes that share an
+ * aligned 16-byte piece with the first or last output byte keep their value.  All absolute
+ * offsets are 64-bit.
+ *
+ * Cost: one byte per slot for the slots that ask for nothing, a 64-byte header read for the
+ * others, two scans over na + nb entries, and a build pass over the emitting slots alone, 8 lanes
+ * each.  Temporary device memory, kept per device between calls: 9 bytes per slot (17 without
+ * slot_off) plus the scans' own.
+ *
+ * Parity: the record layout is pinned by the records of all these types that the reference's own
+ * K2HCommandArchive wrote into the archive fixture of oracle/gen_archive.cc.  That
+ * K2HArchive::Load, replaying the output onto the held table, leaves the new one is shown against
+ * a transliteration of Load (tests/test_ralledata_delta.py); libk2hash itself is not built by this
+ * project's tests, so parity with it is a restatement.  It holds for tables without builtin attrs
+ * and without history, the preconditions of section 5c. */
+#define K2H_AMD_DELTA_SET_ALL 0x01u
+#define K2H_AMD_DELTA_REPLACE_VAL 0x02u
+#define K2H_AMD_DELTA_REPLACE_SKEY 0x04u
+#define K2H_AMD_DELTA_REPLACE_ATTRS 0x08u
+#define K2H_AMD_DELTA_DEL_KEY 0x10u
+int k2h_amd_ralledata_delta(const void* a_blobs, uint64_t a_size, const uint64_t* a_off, uint64_t na,
+                            const uint8_t* rel, const void* b_blobs, uint64_t b_size, const uint64_t* b_off,
+                            uint64_t nb, const uint8_t* b_consider, const uint8_t* seen, void* out, uint64_t out_cap,
+                            uint64_t* slot_off, uint8_t* made, uint64_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------
  * 5. Bulk key streams: keys anywhere in a buffer, and k2hash archives.

@@ -21,6 +21,8 @@ and (2) a batch C ABI backed by hand-written gfx950 HIP kernels (section 2).
              the records that still matter under Load's rule (fold_device, compact_device)
   apply      a transaction log applied to a held blob stream: replication, and log -> snapshot
              (apply_log, apply_records)
+  delta      the inverse: from a held and a new blob stream to the transaction log that turns
+             the one into the other (delta_log, delta_records)
   shard      multi-GPU partitioning and the RCCL gather of hashes
 """
 from .hashfunc import (K2H_2ND_HASH_FUNC, K2H_HASH_FUNC, K2H_HASH_VER_FUNC, K2HashDynLib, k2h_hash,
@@ -29,6 +31,7 @@ from .batch import (bucket_index, hash_csr, hash_csr_host, hash_csr_index, hash_
                     hash_fixed_index, synth_bytes, synth_offsets, unpack_kindex, version)
 from .apply import Applied, apply_log, apply_records
 from .archive import compact_device, fold_device
+from .delta import Delta, delta_log, delta_records
 from .ralledata import (Diff, HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
                         dedup_ralledata, diff_ralledata, import_file_to_archive, import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
                         ralledata_to_archive, route_ralledata, select_ralledata)
@@ -45,4 +48,5 @@ __all__ = [
     "blob_times", "TimeWindow", "Times", "fold_device", "compact_device", "diff_ralledata", "Diff",
     "subkey_edges", "reach_subkeys", "subtree_ralledata", "SubkeyEdges", "Reach",
     "drop_mask", "unlink_subkeys", "prune_ralledata", "Unlinked", "apply_log", "apply_records", "Applied",
+    "delta_log", "delta_records", "Delta",
 ]

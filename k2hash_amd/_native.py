@@ -86,6 +86,8 @@ K2H_AMD_DIFF_ATTRS, K2H_AMD_DIFF_DATA, K2H_AMD_DIFF_REPEAT, K2H_AMD_DIFF_APPLY =
 K2H_AMD_SKEY_PART, K2H_AMD_SKEY_HAS, K2H_AMD_SKEY_BAD = 0x1, 0x2, 0x4
 K2H_AMD_UNLINK_REWRITTEN, K2H_AMD_UNLINK_EMPTIED, K2H_AMD_UNLINK_KEY_ONLY = 0x1, 0x2, 0x4
 K2H_AMD_APPLY_TOUCHED, K2H_AMD_APPLY_SUPERSEDED, K2H_AMD_APPLY_LEFT_OUT = 1, 2, 3
+K2H_AMD_DELTA_SET_ALL, K2H_AMD_DELTA_REPLACE_VAL, K2H_AMD_DELTA_REPLACE_SKEY = 0x01, 0x02, 0x04
+K2H_AMD_DELTA_REPLACE_ATTRS, K2H_AMD_DELTA_DEL_KEY = 0x08, 0x10
 
 _twp = ctypes.POINTER(TimeWindowStruct)
 _dtp = ctypes.POINTER(DiffTimes)
@@ -127,6 +129,8 @@ SIGNATURES = {
     "k2h_amd_import_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_ralledata_archive": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64p, _u64p, _p]),
+    "k2h_amd_ralledata_delta": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _p, _p, _p, _u64, _p, _p,
+                                               _u64p, _p]),
     "k2h_amd_hash_ranges": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_scan": (ctypes.c_int, [_p, _u64, _p, _u64, _p]),
     "k2h_amd_archive_prehash_host": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, ctypes.c_uint32, ctypes.c_int]),

@@ -3,7 +3,8 @@ section 5c): replication without a table.  A peer holds yesterday's elements as 
 receives the K2HTransaction log; apply_log gives the stream that holds the new state -- the held
 blobs no record touches, copied through, then one blob per touched key that still exists.  With an
 empty held stream it turns a log with REPLACE_* and DEL_KEY records into a snapshot, which
-archive_to_ralledata (SET_ALL only) cannot.
+archive_to_ralledata (SET_ALL only) cannot.  delta.delta_log is the inverse: from the held and the new
+stream to the log that, applied here, gives the new stream's elements.
 
 OW_VAL and RENAME are not executed on the device.  The first of them ends the log: ``stop`` is
 its index.  The caller handles that one record itself and calls again with the rest and this

@@ -1203,6 +1203,42 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_archive(const void*
   return rc == K2H_AMD_OK ? rc : fail(rc, "ralledata_archive: the records exceed out_cap, or too many blobs");
 }
 
+// Section 4d': the log that turns the held stream into the new one.  Judged on the host before
+// any device is touched.
+__attribute__((visibility("default"))) int k2h_amd_ralledata_delta(
+    const void* a_blobs, uint64_t a_size, const uint64_t* a_off, uint64_t na, const uint8_t* rel, const void* b_blobs,
+    uint64_t b_size, const uint64_t* b_off, uint64_t nb, const uint8_t* b_consider, const uint8_t* seen, void* out,
+    uint64_t out_cap, uint64_t* slot_off, uint8_t* made, uint64_t* counts, void* stream) {
+  if (!counts) return fail(K2H_AMD_EINVAL, "ralledata_delta: NULL counts");
+  for (int k = 0; k < 8; ++k) counts[k] = 0;
+  if (na && !rel) return fail(K2H_AMD_EINVAL, "ralledata_delta: NULL rel");
+  if (na && !a_blobs) return fail(K2H_AMD_EINVAL, "ralledata_delta: NULL a_blobs");
+  if (na && !a_off) return fail(K2H_AMD_EINVAL, "ralledata_delta: NULL a_off");
+  if (nb && seen && !b_blobs) return fail(K2H_AMD_EINVAL, "ralledata_delta: seen given with NULL b_blobs");
+  if (nb && seen && !b_off) return fail(K2H_AMD_EINVAL, "ralledata_delta: seen given with NULL b_off");
+  if (out && !slot_off && (na || nb)) return fail(K2H_AMD_EINVAL, "ralledata_delta: out given without slot_off");
+  if (na > 0xFFFFFFFEull || nb > 0xFFFFFFFEull - na)
+    return fail(K2H_AMD_EINVAL,
+                "ralledata_delta: more than 2^32 - 2 slots (neither the ranks of the emitting slots nor a launch grid "
+                "would fit)");
+  if (na + nb == 0 && !slot_off) return K2H_AMD_OK;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  if (na + nb == 0) {  // no slot: slot_off[0] = 0
+    e = hipMemsetAsync(slot_off, 0, 8, (hipStream_t)stream);
+    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_delta: hipMemsetAsync", e);
+  }
+  int rc = k2h::launch_ralledata_delta(a_blobs, a_size, a_off, na, rel, b_blobs, b_size, b_off, nb, b_consider, seen, out,
+                                       out_cap, slot_off, made, counts, (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EINVAL) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "ralledata_delta: the %llu bytes of the records exceed out_cap %llu",
+             (unsigned long long)counts[1], (unsigned long long)out_cap);
+    return fail(rc, msg);
+  }
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_delta", e);
+}
+
 __attribute__((visibility("default"))) const char* k2h_amd_version(void) {
   return "k2hash_amd 0.1 (FNV-1A BUILTIN, gfx950 HIP batch kernels)";
 }

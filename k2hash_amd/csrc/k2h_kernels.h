@@ -204,6 +204,16 @@ int launch_ralledata_archive(const void* blobs, uint64_t size, const uint64_t* b
                              const uint8_t* keep, void* out, uint64_t out_cap, uint64_t* rec_off, uint64_t* records,
                              uint64_t* total, hipStream_t stream, hipError_t* herr);
 
+// The log that turns the held stream B into the new stream A (k2h_ralledata_delta.hip), from the
+// rel and seen of launch_ralledata_diff over the two.  Returns a K2H_AMD_* code (the HIP error in
+// *herr) and synchronises the stream once to return counts.  1 <= na + nb <= 2^32 - 2;
+// slot_off given with out.  K2H_AMD_EINVAL: out != NULL and counts[1] > out_cap (counts, slot_off
+// and made are filled).
+int launch_ralledata_delta(const void* a_blobs, uint64_t a_size, const uint64_t* a_off, uint64_t na, const uint8_t* rel,
+                           const void* b_blobs, uint64_t b_size, const uint64_t* b_off, uint64_t nb,
+                           const uint8_t* b_consider, const uint8_t* seen, void* out, uint64_t out_cap, uint64_t* slot_off,
+                           uint8_t* made, uint64_t* counts, hipStream_t stream, hipError_t* herr);
+
 // Keys at arbitrary (start, length) ranges (k2h_ranges.hip); cstr: hash key + NUL.
 hipError_t launch_ranges(const void* base, const uint64_t* starts, const uint64_t* lens, uint64_t n, uint64_t seed,
                          bool cstr, uint64_t* h1, uint64_t* h2, hipStream_t stream);

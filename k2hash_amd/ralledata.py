@@ -569,7 +569,8 @@ def diff_ralledata(a_blobs, a_off, b_blobs, b_off, a_consider=None, b_consider=N
     element, would not return early, and feed is the mask of the blobs worth feeding,
     PART and (REPEAT or (APPLY and (FOUND ? a segment differs : DATA))): feeding them leaves the
     table that feeding all of A leaves, when B holds exactly the table's elements for A's
-    identities.  Held elements A does not mention are reported (seen == 0), never removed.
+    identities.  Held elements A does not mention are only reported here (seen == 0);
+    delta.delta_log turns them into DEL_KEY records.
     count: the four counts, which synchronises the stream once; with count=False the call is
     asynchronous and they are None."""
     torch = _torch()
