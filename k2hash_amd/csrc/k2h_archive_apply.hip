@@ -17,11 +17,9 @@
 //            leaves its W bits and a DEL_KEY bit in the side record's last word.  A considered
 //            OW_VAL or RENAME with status 0 raises the stop word by an atomic max of n - i.
 //   count    participants per tile, the records at or behind the stop taken out: only now is
-//            the stop known.  A scan of the counts and ralle_compact_kernel lay the
-//            (hash, index) pairs out for the sort, participants first in index order.
-//   sort     hipcub::DeviceRadixSort::SortPairs on the hash's low bits (sort_bits_for): stable,
-//            so in a run of equal sorted bits the held entries come first in stream order,
-//            then the records in log order.
+//            the stop known.
+//   sort     the sort stage of k2h_sort_stage.h: stable, so in a run of equal sorted bits the held
+//            entries come first in stream order, then the records in log order.
 //   plan     one lane per sorted position.  Forward to the next entry of the lane's identity.
 //            A held blob that has one is superseded (the next is a held blob) or touched (a
 //            record) and gives up its output bytes.  A record that has none is its
@@ -32,8 +30,8 @@
 //            no open field is passed without a key compare; one that shares only the sorted
 //            bits is stepped over on the hash, one that shares the hash on subhash, length and
 //            key bytes.  The anchor leaves the three sources and the blob's size.
-//   place    two exclusive sums over the slots in index order, sizes into places and emitted
-//            flags into ranks; the counts and the stop come back to the host (the one
+//   place    two exclusive sums over the slots in index order (PlaceRank), sizes into places and
+//            emitted flags into ranks; the counts and the stop come back to the host (the one
 //            synchronisation of the call).
 //   copy     part 1, the held blobs that are emitted unchanged: ralle_place_copy_kernel
 //            (k2h_ralle_copy.h) over the places of the first na slots; place[na] is where
@@ -414,15 +412,13 @@ PerDevice<ApScratch> g_apply;
 constexpr size_t kApPinned = kCounterBytes + 64;  // the counter lines, the stop word, bytes, part-1 blobs, blobs
 
 struct ApCols {
-  uint64_t *keys_in, *keys_out;  // keys_out: first the slots' hashes by index, then the sorted keys
-  uint32_t *idx_in, *idx_out;
+  SortStage<> st;
   Side* side;
   uint8_t* part;
   uint64_t* place;
   uint32_t* rank;
   uint4* plan;
   uint64_t *h1, *h2;
-  uint64_t *tile_count, *tile_base;
   unsigned long long* counter;  // the stop word right behind the lines: one memset clears both
   void* tmp;
   size_t total;
@@ -448,17 +444,12 @@ int launch_archive_apply(const void* held, uint64_t held_size, const uint64_t* h
   const uint64_t N = na + n;
   const uint64_t nt = (N + kApBlock - 1) / kApBlock;
   ApScratch* const scp = g_apply.current(tr);
-  size_t tile_bytes = 0, b8 = 0, b4 = 0, sort_bytes = 0;
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, tile_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b8, (uint64_t*)nullptr, (uint64_t*)nullptr, N + 1, stream));
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b4, (uint32_t*)nullptr, (uint32_t*)nullptr, N + 1, stream));
-  const int sort_bits = sort_bits_for(N);
-  tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, N, 0, sort_bits, stream));
+  SortStage<> st;
+  PlaceRank<> pr;
+  pr.measure(tr, N, stream);
+  st.measure(tr, N, nt, stream);
   if (!tr.ok()) return done(K2H_AMD_OK);
-  size_t tmp_bytes = tile_bytes > sort_bytes ? tile_bytes : sort_bytes;
-  if (b8 > tmp_bytes) tmp_bytes = b8;
-  if (b4 > tmp_bytes) tmp_bytes = b4;
+  const size_t tmp_bytes = std::max(st.tmp_bytes(), pr.tmp_bytes());
   ApScratch& sc = *scp;
   std::lock_guard<std::mutex> lk(sc.mu);
   if (!sc.pinned) tr(hipHostMalloc(&sc.pinned, kApPinned, hipHostMallocDefault));
@@ -467,10 +458,7 @@ int launch_archive_apply(const void* held, uint64_t held_size, const uint64_t* h
   auto layout = [&](void* base) {
     Carver c(base);
     ApCols k;
-    k.keys_in = c.take<uint64_t>(N);
-    k.keys_out = c.take<uint64_t>(N);
-    k.idx_in = c.take<uint32_t>(N);
-    k.idx_out = c.take<uint32_t>(N);
+    k.st = st.take(c);
     k.side = c.take<Side>(N);
     k.part = c.take<uint8_t>(N);
     k.place = c.take<uint64_t>(N + 1);
@@ -478,8 +466,6 @@ int launch_archive_apply(const void* held, uint64_t held_size, const uint64_t* h
     k.plan = c.take<uint4>(n);
     k.h1 = c.take<uint64_t>(h1 ? 0 : n);
     k.h2 = c.take<uint64_t>(h1 ? 0 : n);
-    k.tile_count = c.take<uint64_t>(nt + 1);
-    k.tile_base = c.take<uint64_t>(nt + 1);
     k.counter = (unsigned long long*)c.bytes(kCounterBytes + 8);
     k.tmp = c.bytes(tmp_bytes);
     k.total = c.total();
@@ -490,8 +476,7 @@ int launch_archive_apply(const void* held, uint64_t held_size, const uint64_t* h
   unsigned long long* const stopw = k.counter + kCounterBytes / 8;
   const unsigned grid = (unsigned)nt;
 
-  // entry nt of the counts is 0, so entry nt of their exclusive scan is the participants' number
-  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  k.st.clear(tr, stream);
   tr(hipMemsetAsync(k.counter, 0, kCounterBytes + 8, stream));
   if (tr.ok() && !h1 && n) {
     ArchiveHashOut ho;
@@ -501,30 +486,23 @@ int launch_archive_apply(const void* held, uint64_t held_size, const uint64_t* h
   const ApIn s{(const uint8_t*)held, held_size, held_off, na,          held_keep,        (const uint8_t*)file,
                size,                 recs,      n,        consider,    h1 ? h1 : k.h1,   h1 ? h2 : k.h2};
   if (tr.ok()) {
-    apply_gather_kernel<<<(unsigned)(N / kApBlock + 1), kApBlock, 0, stream>>>(s, k.part, k.keys_out, k.side, k.place,
+    apply_gather_kernel<<<(unsigned)(N / kApBlock + 1), kApBlock, 0, stream>>>(s, k.part, k.st.hashes(), k.side, k.place,
                                                                                k.rank, touched, stopw);
     tr(hipGetLastError());
   }
   if (tr.ok()) {
-    apply_count_kernel<<<grid, kApBlock, 0, stream>>>(k.part, na, n, stopw, k.tile_count);
+    apply_count_kernel<<<grid, kApBlock, 0, stream>>>(k.part, na, n, stopw, k.st.tile_count);
     tr(hipGetLastError());
   }
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tile_bytes, k.tile_count, k.tile_base, nt + 1, stream));
+  k.st.scan_tiles(tr, k.tmp, stream);
+  ralle_compact<kApBlock>(tr, k.st, k.part, N, 0, stream);
+  k.st.sort(tr, k.tmp, stream);
   if (tr.ok()) {
-    ralle_compact_kernel<kApBlock><<<grid, kApBlock, 0, stream>>>(k.part, k.keys_out, N, k.tile_base, nt, 0, k.keys_in,
-                                                                  k.idx_in);
+    apply_plan_kernel<<<grid, kApBlock, kPlanLds, stream>>>(s, k.st.keys_out, k.st.idx_out, k.st.mask(), k.side, k.place,
+                                                            k.rank, k.plan, touched, k.counter);
     tr(hipGetLastError());
   }
-  if (tr.ok())
-    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
-                                          (const uint32_t*)k.idx_in, k.idx_out, N, 0, sort_bits, stream));
-  if (tr.ok()) {
-    apply_plan_kernel<<<grid, kApBlock, kPlanLds, stream>>>(s, k.keys_out, k.idx_out, sort_mask(sort_bits), k.side,
-                                                            k.place, k.rank, k.plan, touched, k.counter);
-    tr(hipGetLastError());
-  }
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b8, k.place, k.place, N + 1, stream));
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b4, k.rank, k.rank, N + 1, stream));
+  pr.scan(tr, k.tmp, k.place, k.rank, stream);
   unsigned long long* const tail = host + kCounterBytes / 8;  // stop word, bytes, part-1 blobs | blobs
   if (tr.ok()) tr(hipMemcpyAsync(host, k.counter, kCounterBytes + 8, hipMemcpyDeviceToHost, stream));
   if (tr.ok()) tr(hipMemcpyAsync(tail + 1, k.place + N, 8, hipMemcpyDeviceToHost, stream));

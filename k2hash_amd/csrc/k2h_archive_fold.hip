@@ -12,14 +12,12 @@
 // Stages, all on the caller's stream:
 //   gather   one lane per record: participant or not, its W bits and barrier bit, a 32-byte
 //            side record (key offset, key length, bits), the first cover summary (nothing
-//            behind it).  A scan of the tiles' packed counts (participants in the low half,
-//            RENAME participants in the high half) and a second kernel give every participant
-//            its seg -- the RENAMEs before it -- and lay the (h1, index) pairs out for the
-//            sort: participants first, in record order, every other record behind them as
-//            (~0, kNone), so that a non-participant ends every walk that reaches it.
-//   sort     hipcub::DeviceRadixSort::SortPairs over (h1, index) on the hash's low bits only
-//            (sort_bits_for, the reasoning of k2h_ralledata_dedup.hip): stable, so records of
-//            one hash are neighbours in record order.
+//            behind it), and the tile's packed count: participants in the low half, RENAME
+//            participants in the high half.
+//   sort     the sort stage of k2h_sort_stage.h over (h1, index), with this file's own compact
+//            kernel, which also gives every participant its seg -- the RENAMEs before it -- from
+//            the high half of the scanned counts.  Stable, so records of one hash are neighbours
+//            in record order.
 //   link     one lane per sorted position: forward to the nearest later entry of the same full
 //            h1, key length and key bytes -- `by` -- and from it the lane's first summary
 //            (U, nxt): U = W(by), nxt = by; or nothing when by is absent, a barrier or in
@@ -54,7 +52,7 @@
 
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
-#include "k2h_scratch.h"
+#include "k2h_sort_stage.h"
 
 // Dynamic LDS, never touched, that a build can give to the link and cover kernels so that fewer
 // blocks fit a CU: 64 KiB leaves two 256-thread blocks per CU, two waves per SIMD; 0 leaves
@@ -268,11 +266,9 @@ PerDevice<> g_fold;
 constexpr size_t kFlagBytes = 256;  // kMaxRounds + 1 words
 
 struct FoldCols {
-  uint64_t *keys_in, *keys_out;  // keys_out: first the records' own hashes (h1 == NULL), then the sorted keys
+  SortStage<> st;  // hashes(): the records' own hashes when h1 == NULL
   uint64_t *sum_a, *sum_b;
-  uint32_t *idx_in, *idx_out;
   Side* side;
-  uint64_t *tile_count, *tile_base;
   uint32_t* flags;
   unsigned long long* counter;  // right behind the flags: one memset clears both
   void* tmp;
@@ -289,11 +285,8 @@ int launch_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_r
   const uint64_t nt = (n + kFoldRecs - 1) / kFoldRecs;
   FirstError tr;
   DeviceScratch* const sc = g_fold.current(tr);
-  size_t scan_bytes = 0, sort_bytes = 0;
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
-  const int sort_bits = sort_bits_for(n);
-  tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
+  SortStage<> st;
+  st.measure(tr, n, nt, stream);
   if (!tr.ok()) {
     *herr = tr.e;
     return K2H_AMD_EHIP;
@@ -301,18 +294,13 @@ int launch_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_r
   auto layout = [&](void* base) {
     Carver c(base);
     FoldCols k;
-    k.keys_in = c.take<uint64_t>(n);
-    k.keys_out = c.take<uint64_t>(n);
+    k.st = st.take(c);
     k.sum_a = c.take<uint64_t>(n);
     k.sum_b = c.take<uint64_t>(n);
-    k.idx_in = c.take<uint32_t>(n);
-    k.idx_out = c.take<uint32_t>(n);
     k.side = c.take<Side>(n);
-    k.tile_count = c.take<uint64_t>(nt + 1);
-    k.tile_base = c.take<uint64_t>(nt + 1);
     k.flags = (uint32_t*)c.bytes(kFlagBytes);
     k.counter = (unsigned long long*)c.bytes(kCounterBytes);
-    k.tmp = c.bytes(scan_bytes > sort_bytes ? scan_bytes : sort_bytes);
+    k.tmp = c.bytes(st.tmp_bytes());
     k.total = c.total();
     return k;
   };
@@ -320,31 +308,27 @@ int launch_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_r
   if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
   const FoldCols k = layout(sc->p);
   const unsigned grid = (unsigned)nt;
-  // entry nt of the counts is 0, so entry nt of their exclusive scan is the totals
-  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  k.st.clear(tr, stream);
   tr(hipMemsetAsync(k.flags, 0, kFlagBytes + kCounterBytes, stream));
   if (tr.ok() && !h1) {
     ArchiveHashOut ho;
-    ho.h1 = k.keys_out;
+    ho.h1 = k.st.hashes();
     tr(launch_archive_prehash(file, size, recs, n, seed, ho, stream));
   }
   if (tr.ok()) {
-    archive_fold_gather_kernel<<<grid, kFoldRecs, 0, stream>>>(recs, size, n, keep, by, k.side, k.sum_a, k.tile_count);
+    archive_fold_gather_kernel<<<grid, kFoldRecs, 0, stream>>>(recs, size, n, keep, by, k.side, k.sum_a, k.st.tile_count);
     tr(hipGetLastError());
   }
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, scan_bytes, k.tile_count, k.tile_base, nt + 1, stream));
+  k.st.scan_tiles(tr, k.tmp, stream);
   if (tr.ok()) {
-    archive_fold_compact_kernel<<<grid, kFoldRecs, 0, stream>>>(keep, h1 ? h1 : k.keys_out, n, k.tile_base, nt, k.side,
-                                                               k.keys_in, k.idx_in);
+    archive_fold_compact_kernel<<<grid, kFoldRecs, 0, stream>>>(keep, h1 ? h1 : k.st.hashes(), n, k.st.tile_base, nt,
+                                                               k.side, k.st.keys_in, k.st.idx_in);
     tr(hipGetLastError());
   }
-  if (tr.ok())
-    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
-                                          (const uint32_t*)k.idx_in, k.idx_out, n, 0, sort_bits, stream));
+  k.st.sort(tr, k.tmp, stream);
   if (tr.ok()) {
-    const uint64_t mask = sort_mask(sort_bits);
-    archive_fold_link_kernel<<<grid, kFoldRecs, kLinkLds, stream>>>((const uint8_t*)file, k.keys_out, k.idx_out, n,
-                                                                    mask, k.side, by, k.sum_a, k.flags);
+    archive_fold_link_kernel<<<grid, kFoldRecs, kLinkLds, stream>>>((const uint8_t*)file, k.st.keys_out, k.st.idx_out, n,
+                                                                    k.st.mask(), k.side, by, k.sum_a, k.flags);
     tr(hipGetLastError());
   }
   // the rounds: flags[r] says whether the kernel before round r left a lane unfinished

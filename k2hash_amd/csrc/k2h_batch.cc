@@ -42,6 +42,20 @@ uint64_t seed_for(uint32_t flags) {
   return (flags & K2H_AMD_FLAG_STD_FNV) ? k2h::kSeedStd : k2h::kSeedBuiltin;
 }
 
+// A launcher's K2H_AMD_EINVAL: the `bytes` it counted for `what` do not fit the caller's out_cap.
+int exceeds_cap(const char* who, const char* what, uint64_t bytes, uint64_t cap) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: the %llu bytes of the %s exceed out_cap %llu", who, (unsigned long long)bytes, what,
+           (unsigned long long)cap);
+  return fail(K2H_AMD_EINVAL, msg);
+}
+
+// The whole answer of a call over nothing: its one offset, 0, written on the stream.
+int clear_word(uint64_t* word, void* stream, const char* what) {
+  const hipError_t e = hipMemsetAsync(word, 0, 8, (hipStream_t)stream);
+  return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, what, e);
+}
+
 // ---------------------------------------------------------------------------
 // Device gate (include/k2hash_amd.h: K2H_AMD_ENODEV = "no usable gfx950 device").  The
 // library carries gfx950 code objects only, so every entry point that launches checks the
@@ -721,19 +735,11 @@ __attribute__((visibility("default"))) int k2h_amd_archive_apply(
   if (na + n == 0 && !out_off) return K2H_AMD_OK;
   K2H_GATE();
   hipError_t e = hipSuccess;
-  if (na + n == 0) {  // nothing held, no log: out_off[0] = 0
-    e = hipMemsetAsync(out_off, 0, 8, (hipStream_t)stream);
-    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "archive_apply: hipMemsetAsync", e);
-  }
+  if (na + n == 0) return clear_word(out_off, stream, "archive_apply: hipMemsetAsync");  // nothing held, no log
   int rc = k2h::launch_archive_apply(held, held_size, held_off, na, held_keep, file, size, recs, n, consider, h1, h2,
                                      seed_for(flags), out, out_cap, out_off, origin, touched, counts, stop,
                                      (hipStream_t)stream, &e);
-  if (rc == K2H_AMD_EINVAL) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "archive_apply: the %llu bytes of the emitted blobs exceed out_cap %llu",
-             (unsigned long long)counts[1], (unsigned long long)out_cap);
-    return fail(rc, msg);
-  }
+  if (rc == K2H_AMD_EINVAL) return exceeds_cap("archive_apply", "emitted blobs", counts[1], out_cap);
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_archive_apply", e);
 }
 
@@ -987,10 +993,7 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_subkeys(
   if (n == 0 && !edge_off) return K2H_AMD_OK;
   K2H_GATE();
   hipError_t e = hipSuccess;
-  if (n == 0) {  // no blob, no edge: edge_off[0] = 0
-    e = hipMemsetAsync(edge_off, 0, 8, (hipStream_t)stream);
-    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_subkeys: hipMemsetAsync", e);
-  }
+  if (n == 0) return clear_word(edge_off, stream, "ralledata_subkeys: hipMemsetAsync");  // no blob, no edge
   int why = 0;
   int rc = k2h::launch_ralledata_subkeys(blobs, size, blob_off, n, consider, seed_for(flags), sk_flags, edge_off, rep,
                                          child, cap, counts, &why, (hipStream_t)stream, &e);
@@ -1047,18 +1050,10 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_unlink(
   if (n == 0 && !out_off) return K2H_AMD_OK;
   K2H_GATE();
   hipError_t e = hipSuccess;
-  if (n == 0) {  // no blob: out_off[0] = 0
-    e = hipMemsetAsync(out_off, 0, 8, (hipStream_t)stream);
-    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_unlink: hipMemsetAsync", e);
-  }
+  if (n == 0) return clear_word(out_off, stream, "ralledata_unlink: hipMemsetAsync");  // no blob
   int rc = k2h::launch_ralledata_unlink(blobs, size, blob_off, n, keep, sk_flags, edge_off, drop, out, out_cap, out_off,
                                         index, changed, counts, (hipStream_t)stream, &e);
-  if (rc == K2H_AMD_EINVAL) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "ralledata_unlink: the %llu bytes of the emitted blobs exceed out_cap %llu",
-             (unsigned long long)counts[1], (unsigned long long)out_cap);
-    return fail(rc, msg);
-  }
+  if (rc == K2H_AMD_EINVAL) return exceeds_cap("ralledata_unlink", "emitted blobs", counts[1], out_cap);
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_unlink", e);
 }
 
@@ -1130,8 +1125,7 @@ int recs_ralledata_args(const char* who, const void* file, uint64_t size, const 
     *rc = K2H_AMD_OK;
     if (blob_off) {
       if ((*rc = gate_current())) return 1;
-      hipError_t e = hipMemsetAsync(blob_off, 0, 8, (hipStream_t)stream);
-      if (e != hipSuccess) *rc = fail(K2H_AMD_EHIP, who, e);
+      *rc = clear_word(blob_off, stream, who);
     }
     return 1;
   }
@@ -1186,8 +1180,7 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_archive(const void*
   if (n == 0) {
     if (!rec_off) return K2H_AMD_OK;
     K2H_GATE();
-    hipError_t e = hipMemsetAsync(rec_off, 0, 8, (hipStream_t)stream);
-    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_archive", e);
+    return clear_word(rec_off, stream, "ralledata_archive");
   }
   if (!rec_off) return fail(K2H_AMD_EINVAL, "ralledata_archive: NULL rec_off");
   if (!blobs) return fail(K2H_AMD_EINVAL, "ralledata_archive: NULL blobs");
@@ -1224,18 +1217,10 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_delta(
   if (na + nb == 0 && !slot_off) return K2H_AMD_OK;
   K2H_GATE();
   hipError_t e = hipSuccess;
-  if (na + nb == 0) {  // no slot: slot_off[0] = 0
-    e = hipMemsetAsync(slot_off, 0, 8, (hipStream_t)stream);
-    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_delta: hipMemsetAsync", e);
-  }
+  if (na + nb == 0) return clear_word(slot_off, stream, "ralledata_delta: hipMemsetAsync");  // no slot
   int rc = k2h::launch_ralledata_delta(a_blobs, a_size, a_off, na, rel, b_blobs, b_size, b_off, nb, b_consider, seen, out,
                                        out_cap, slot_off, made, counts, (hipStream_t)stream, &e);
-  if (rc == K2H_AMD_EINVAL) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "ralledata_delta: the %llu bytes of the records exceed out_cap %llu",
-             (unsigned long long)counts[1], (unsigned long long)out_cap);
-    return fail(rc, msg);
-  }
+  if (rc == K2H_AMD_EINVAL) return exceeds_cap("ralledata_delta", "records", counts[1], out_cap);
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_delta", e);
 }
 

@@ -1,12 +1,11 @@
 // k2hash_amd -- a blob's identity as the kernels that sort blobs by their stored hash hold and
-// compare it (k2h_ralledata_dedup.hip, k2h_ralledata_diff.hip, k2h_ralledata_subkeys.hip): the
-// side record a gather leaves per participant, the end-aligned 16-byte compare of two byte ranges
-// of one length.  Below those, the join's machinery in the form k2h_ralledata_subkeys.hip
-// launches it: the kernel that lays the pairs out for the sort, the mark kernel and max-scan
-// operator, and the backward walk to the last held entry of an identity.
-// k2h_ralledata_dedup.hip and k2h_ralledata_diff.hip, from which these were lifted, launch the
-// same ones.  The number of hash bits the pairs are sorted by and the launchers' scratch are in
-// k2h_layout.h and k2h_scratch.h.
+// compare it (dedup, diff, subkeys, apply): the side record a gather leaves per participant and the
+// end-aligned 16-byte compare of two byte ranges of one length.  Below those, the kernels on either
+// side of the sort stage (k2h_sort_stage.h has the stage's order and the library calls) with the
+// host helpers that launch them from a SortStage: the compact kernel that lays the pairs out for
+// the sort, the mark kernel that feeds the max-scan (diff, subkeys), and the backward walk to the
+// last held entry of an identity.  k2h_archive_fold.hip has a side record and a compact kernel of
+// its own and does not include this header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -16,6 +15,7 @@
 #include "k2h_endwalk.h"
 #include "k2h_kernels.h"
 #include "k2h_scratch.h"
+#include "k2h_sort_stage.h"
 
 namespace k2h {
 
@@ -87,9 +87,23 @@ __global__ __launch_bounds__(BLOCK) void ralle_mark_kernel(const uint32_t* __res
   if (p < n) mark[p] = idx[p] < nb ? (uint32_t)(p + 1) : 0u;
 }
 
-struct RalleMaxU32 {
-  __host__ __device__ __forceinline__ uint32_t operator()(uint32_t x, uint32_t y) const { return x > y ? x : y; }
-};
+// The two launched from a stage: the pairs of the n slots with participant bytes `part` into the
+// sort's input; the sorted entries below `held` marked in the stage's mark column.
+template <int BLOBS>
+void ralle_compact(FirstError& tr, const SortStage<>& st, const uint8_t* part, uint64_t n, uint64_t extra,
+                   hipStream_t stream) {
+  if (!tr.ok()) return;
+  ralle_compact_kernel<BLOBS><<<(unsigned)st.tiles, BLOBS, 0, stream>>>(part, st.hashes(), n, st.tile_base, st.tiles,
+                                                                      extra, st.keys_in, st.idx_in);
+  tr(hipGetLastError());
+}
+template <int BLOCK>
+void ralle_mark(FirstError& tr, const SortStage<>& st, uint64_t held, hipStream_t stream) {
+  if (!tr.ok()) return;
+  ralle_mark_kernel<BLOCK><<<(unsigned)((st.pairs + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(st.idx_out, st.pairs, held,
+                                                                                           st.mark());
+  tr(hipGetLastError());
+}
 
 // The last held entry (index below nb) with the identity of `sa` and hash h: backward from
 // sorted position q0 (1 + a position, 0: none) over the run's held entries while the sorted

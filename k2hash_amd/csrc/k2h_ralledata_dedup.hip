@@ -18,17 +18,13 @@
 // The kernels are templates on that bool; the plain rule's instantiations are the code they
 // were.
 //
-// Three stages, all on the caller's stream:
+// Three stages, all on the caller's stream (the scan, compact and sort between gather and resolve
+// are the sort stage of k2h_sort_stage.h):
 //   gather   one lane per blob: span, header and classify (k2h_ralle_header.h, shared with
 //            the check kernel); a participant leaves its stored hash and a 32-byte side
-//            record (subhash, absolute key offset, key length, attrs bit).  A scan of the
-//            tiles' participant counts and a second kernel lay the (hash, index) pairs out
-//            for the sort: participants first, in stream order, every other blob behind
-//            them as (~0, kNone) -- so a non-participant sorts behind every participant of
-//            any hash and ends every walk that reaches it.
-//   sort     hipcub::DeviceRadixSort::SortPairs over (hash, index), on the hash's low bits
-//            only (sort_bits_for): stable, so blobs of one stored hash are neighbours in
-//            stream order, now and then with a blob of another hash among them.
+//            record (subhash, absolute key offset, key length, attrs bit), a tile its count.
+//   sort     the (hash, index) pairs on the hash's low bits: blobs of one stored hash are
+//            neighbours in stream order, now and then with a blob of another hash among them.
 //   resolve  one lane per sorted position p.  Other sorted bits at p + 1: the blob is kept
 //            and nothing more is read.  Else the lane walks forward from p + 1 to the first
 //            entry with its hash, subhash, key length and key bytes -- `by` -- and applies
@@ -168,16 +164,14 @@ __global__ __launch_bounds__(kResolveBlock) void ralledata_dedup_resolve_kernel(
   }
 }
 
-// The call's temporaries (k2h_scratch.h) -- 56 bytes per blob (two key and two index columns, the
-// side records), the tile counts and their scan, the counters, and the library's own storage;
-// the mtime rule adds 16 bytes per blob behind them.
+// The call's temporaries (k2h_scratch.h) -- 56 bytes per blob (the stage's two key and two index
+// columns, the side records), the tile counts and their scan, the counters, and the library's own
+// storage; the mtime rule adds 16 bytes per blob behind them.
 PerDevice<> g_dedup;
 
 struct DedupCols {
-  uint64_t *keys_in, *keys_out;  // keys_out: first the blobs' hashes by blob index, then the sorted keys
-  uint32_t *idx_in, *idx_out;
+  SortStage<> st;
   Side* side;
-  uint64_t *tile_count, *tile_base;
   unsigned long long* counter;
   void* tmp;
   Mtime* mt;  // the mtime rule only, behind everything else: the plain rule's layout stays
@@ -192,11 +186,8 @@ int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uin
   const uint64_t nt = (n + kDedupBlobs - 1) / kDedupBlobs;
   FirstError tr;
   DeviceScratch* const sc = g_dedup.current(tr);
-  size_t scan_bytes = 0, sort_bytes = 0;
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
-  const int sort_bits = sort_bits_for(n);
-  tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
+  SortStage<> st;
+  st.measure(tr, n, nt, stream);
   if (!tr.ok()) {
     *herr = tr.e;
     return K2H_AMD_EHIP;
@@ -204,15 +195,10 @@ int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uin
   auto layout = [&](void* base) {
     Carver c(base);
     DedupCols k;
-    k.keys_in = c.take<uint64_t>(n);
-    k.keys_out = c.take<uint64_t>(n);
-    k.idx_in = c.take<uint32_t>(n);
-    k.idx_out = c.take<uint32_t>(n);
+    k.st = st.take(c);
     k.side = c.take<Side>(n);
-    k.tile_count = c.take<uint64_t>(nt + 1);
-    k.tile_base = c.take<uint64_t>(nt + 1);
     k.counter = (unsigned long long*)c.bytes(kCounterBytes);
-    k.tmp = c.bytes(scan_bytes > sort_bytes ? scan_bytes : sort_bytes);
+    k.tmp = c.bytes(st.tmp_bytes());
     k.mt = pts ? c.take<Mtime>(n) : nullptr;
     k.total = c.total();
     return k;
@@ -220,38 +206,31 @@ int dedup_stages(const void* blobs, uint64_t size, const uint64_t* blob_off, uin
   std::lock_guard<std::mutex> lk(sc->mu);
   if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
   const DedupCols k = layout(sc->p);
-  // entry nt of the counts is 0, so entry nt of their exclusive scan is the participants' number
-  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  k.st.clear(tr, stream);
   tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
   if (tr.ok()) {
     if (pts)
       ralledata_dedup_gather_kernel<true><<<(unsigned)nt, kDedupBlobs, kWalkLdsBytes, stream>>>(
-          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, k.keys_out, k.side, k.tile_count, k.mt);
+          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, k.st.hashes(), k.side, k.st.tile_count, k.mt);
     else
       ralledata_dedup_gather_kernel<false><<<(unsigned)nt, kDedupBlobs, 0, stream>>>(
-          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, k.keys_out, k.side, k.tile_count, nullptr);
+          (const uint8_t*)blobs, size, blob_off, n, consider, keep, by, k.st.hashes(), k.side, k.st.tile_count, nullptr);
     tr(hipGetLastError());
   }
-  if (tr.ok())
-    tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, scan_bytes, k.tile_count, k.tile_base, nt + 1, stream));
-  if (tr.ok()) {
-    ralle_compact_kernel<kDedupBlobs><<<(unsigned)nt, kDedupBlobs, 0, stream>>>(keep, k.keys_out, n, k.tile_base, nt, 0,
-                                                                               k.keys_in, k.idx_in);
-    tr(hipGetLastError());
-  }
-  if (tr.ok())
-    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
-                                          (const uint32_t*)k.idx_in, k.idx_out, n, 0, sort_bits, stream));
+  k.st.scan_tiles(tr, k.tmp, stream);
+  ralle_compact<kDedupBlobs>(tr, k.st, keep, n, 0, stream);
+  k.st.sort(tr, k.tmp, stream);
   if (tr.ok()) {
     const uint64_t grid = (n + kResolveBlock - 1) / kResolveBlock;
-    const uint64_t mask = sort_mask(sort_bits);
+    const uint64_t mask = k.st.mask();
     if (pts)
       ralledata_dedup_resolve_kernel<true><<<(unsigned)grid, kResolveBlock, 0, stream>>>(
-          (const uint8_t*)blobs, k.keys_out, k.idx_out, n, mask, k.side, keep, by, k.counter,
+          (const uint8_t*)blobs, k.st.keys_out, k.st.idx_out, n, mask, k.side, keep, by, k.counter,
           MtimeRule{k.mt, pts->sec, pts->nsec});
     else
       ralledata_dedup_resolve_kernel<false><<<(unsigned)grid, kResolveBlock, 0, stream>>>(
-          (const uint8_t*)blobs, k.keys_out, k.idx_out, n, mask, k.side, keep, by, k.counter, MtimeRule{nullptr, 0, 0});
+          (const uint8_t*)blobs, k.st.keys_out, k.st.idx_out, n, mask, k.side, keep, by, k.counter,
+          MtimeRule{nullptr, 0, 0});
     tr(hipGetLastError());
   }
   unsigned long long counts[kCounterBytes / 8];

@@ -16,7 +16,7 @@
 //            memory safety does not rest on rel or seen.  It leaves the slot's bytes, its emit
 //            flag and its made byte, and counts the records per type and the refused slots by
 //            per-wave ballots into the counter lines (k2h_layout.h).
-//   place    two exclusive sums over the slots, bytes into slot_off and emit flags into ranks;
+//   place    PlaceRank (k2h_sort_stage.h) over the slots, bytes into slot_off and emit flags into ranks;
 //            the counts come back to the host (the one synchronisation of the call).
 //   compact  the emitting slots into a list, each at its rank.
 //   build    over the list only: 8 lanes per emitting slot, 32 slots per block.  The record
@@ -33,7 +33,6 @@
 // out[0, total), slot_off[0 .. na + nb] and made[0, na + nb) is written.  All absolute offsets
 // are 64-bit.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include <mutex>
@@ -307,11 +306,9 @@ int launch_ralledata_delta(const void* a_blobs, uint64_t a_size, const uint64_t*
   };
   const uint64_t N = na + nb;
   DeltaScratch* const scp = g_delta.current(tr);
-  size_t b8 = 0, b4 = 0;
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b8, (uint64_t*)nullptr, (uint64_t*)nullptr, N + 1, stream));
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b4, (uint32_t*)nullptr, (uint32_t*)nullptr, N + 1, stream));
+  PlaceRank<> pr;
+  pr.measure(tr, N, stream);
   if (!tr.ok()) return done(K2H_AMD_OK);
-  const size_t tmp_bytes = b8 > b4 ? b8 : b4;
   DeltaScratch& sc = *scp;
   std::lock_guard<std::mutex> lk(sc.mu);
   if (!sc.pinned) tr(hipHostMalloc(&sc.pinned, kDeltaPinned, hipHostMallocDefault));
@@ -325,7 +322,7 @@ int launch_ralledata_delta(const void* a_blobs, uint64_t a_size, const uint64_t*
     k.list = c.take<uint32_t>(N);
     k.mine = c.take<uint8_t>(N);
     k.counter = (unsigned long long*)c.bytes(kCounterBytes);
-    k.tmp = c.bytes(tmp_bytes);
+    k.tmp = c.bytes(pr.tmp_bytes());
     k.total = c.total();
     return k;
   };
@@ -341,8 +338,7 @@ int launch_ralledata_delta(const void* a_blobs, uint64_t a_size, const uint64_t*
                                                                                    k.counter);
     tr(hipGetLastError());
   }
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b8, place, place, N + 1, stream));
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b4, k.rank, k.rank, N + 1, stream));
+  pr.scan(tr, k.tmp, place, k.rank, stream);
   unsigned long long* const tail = host + kCounterBytes / 8;  // bytes | emitting slots
   if (tr.ok()) tr(hipMemcpyAsync(host, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
   if (tr.ok()) tr(hipMemcpyAsync(tail, place + N, 8, hipMemcpyDeviceToHost, stream));

@@ -9,16 +9,15 @@
 // matched blob's attrs as the existing element's: whether the call would go on to write.
 //
 // Both streams share one index space, B at [0, nb) and A at [nb, nb + na).  Four stages, all
-// on the caller's stream:
+// on the caller's stream (the scan, compact and sort behind the gather and the max-scan are the
+// sort stage of k2h_sort_stage.h):
 //   gather   one lane per blob of B, then of A: span, header and classify (k2h_ralle_header.h);
 //            a participant leaves its stored hash and a side record (k2h_ralle_ident.h) whose
 //            last word holds its flags; with times it also has its attrs walked
 //            (k2h_ralle_attrs.h) and leaves its mtime, and a blob of B whether it is expired
-//            at `now`.  A scan of the tiles' participant counts and the compact kernel lay the
-//            (hash, index) pairs out for the sort, participants first in index order.
-//   sort     hipcub::DeviceRadixSort::SortPairs on the hash's low bits (sort_bits_for): stable,
-//            so within a run of equal sorted bits all of B's entries come first, in stream
-//            order, followed by A's in stream order.
+//            at `now`.
+//   sort     stable, so within a run of equal sorted bits all of B's entries come first, in
+//            stream order, followed by A's in stream order.
 //   resolve  a mark kernel and one inclusive max-scan give every sorted position the nearest
 //            B entry at or before it.  One lane per sorted A entry starts there and walks
 //            BACKWARD over B's entries while the sorted bits agree, to the first one of its
@@ -316,20 +315,17 @@ __global__ __launch_bounds__(kDiffBlobs) void ralledata_diff_compare_kernel(Diff
 static_assert(K2H_AMD_DIFF_SKEY == K2H_AMD_DIFF_VAL << 1 && K2H_AMD_DIFF_ATTRS == K2H_AMD_DIFF_VAL << 2,
               "the three differ bits in segment order");
 
-// The call's temporaries (k2h_scratch.h).  With n = na + nb: two key and two index columns and the side
-// records (56 n bytes), a participant byte per blob, the tile counts and their scan, the
-// counters and the library's own storage; with times 16 n more for the mtimes.  The scan column
-// and the work items need none of their own: after the sort its input columns are free, and the
-// mark column takes the index column's place, the scanned positions and the na work items the
-// two halves of the key column's.
+// The call's temporaries (k2h_scratch.h).  With n = na + nb: the stage's two key and two index
+// columns and the side records (56 n bytes), a participant byte per blob, the tile counts and
+// their scan, the counters and the library's own storage; with times 16 n more for the mtimes.
+// The scan column and the na work items need none of their own: they stand in the stage's input
+// columns (SortStage::scanned, ::second; n * 4 >= na * 4 bytes).
 PerDevice<> g_diff;
 
 struct DiffCols {
-  uint64_t *keys_in, *keys_out;  // keys_out: first the blobs' hashes by index, then the sorted keys
-  uint32_t *idx_in, *idx_out;
+  SortStage<> st;
   Side* side;
   uint8_t* part;
-  uint64_t *tile_count, *tile_base;
   unsigned long long* counter;
   void* tmp;
   DiffMtime* mt;  // with times only, behind everything else
@@ -349,32 +345,21 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
   const uint64_t nt = (n + kDiffBlobs - 1) / kDiffBlobs;
   FirstError tr;
   DeviceScratch* const sc = g_diff.current(tr);
-  size_t scan_bytes = 0, sort_bytes = 0, max_bytes = 0;
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
-  const int sort_bits = sort_bits_for(n);
-  tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, sort_bits, stream));
-  tr(hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                       RalleMaxU32(), n, stream));
+  SortStage<> st;
+  st.measure(tr, n, nt, stream);
+  st.measure_max_scan(tr, stream);
   if (!tr.ok()) {
     *herr = tr.e;
     return K2H_AMD_EHIP;
   }
-  size_t tmp_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-  if (max_bytes > tmp_bytes) tmp_bytes = max_bytes;
   auto layout = [&](void* base) {
     Carver c(base);
     DiffCols k;
-    k.keys_in = c.take<uint64_t>(n);
-    k.keys_out = c.take<uint64_t>(n);
-    k.idx_in = c.take<uint32_t>(n);
-    k.idx_out = c.take<uint32_t>(n);
+    k.st = st.take(c);
     k.side = c.take<Side>(n);
     k.part = c.take<uint8_t>(n);
-    k.tile_count = c.take<uint64_t>(nt + 1);
-    k.tile_base = c.take<uint64_t>(nt + 1);
     k.counter = (unsigned long long*)c.bytes(kCounterBytes);
-    k.tmp = c.bytes(tmp_bytes);
+    k.tmp = c.bytes(st.tmp_bytes());
     k.mt = c.take<DiffMtime>(times ? n : 0);
     k.total = c.total();
     return k;
@@ -382,54 +367,39 @@ int launch_ralledata_diff(const void* a_blobs, uint64_t a_size, const uint64_t* 
   std::lock_guard<std::mutex> lk(sc->mu);
   if (const int rc = sc->reserve(layout(nullptr).total, stream, herr)) return rc;
   const DiffCols k = layout(sc->p);
-  // free once the sort has read them, its input columns: the mark column takes the index column's
-  // place, the scanned positions the first half of the key column's and the na work items the
-  // second (n * 4 >= na * 4 bytes)
-  uint32_t* mark = k.idx_in;
-  uint32_t* last_b = (uint32_t*)k.keys_in;
-  uint32_t* work = last_b + n;
+  uint32_t* const last_b = k.st.scanned();
+  uint32_t* const work = k.st.second();
 
   const DiffStream sa{(const uint8_t*)a_blobs, a_size, a_off, a_consider};
   const DiffStream sb{(const uint8_t*)b_blobs, b_size, b_off, b_consider};
   DiffTimes tm{k.mt, 0, 0, 0, 0};
   if (times) tm = DiffTimes{k.mt, times->pts.sec, times->pts.nsec, times->now.sec, times->now.nsec};
-  // entry nt of the counts is 0, so entry nt of their exclusive scan is the participants' number
-  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  k.st.clear(tr, stream);
   tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
   if (seen && nb) tr(hipMemsetAsync(seen, 0, nb, stream));
   if (tr.ok()) {
     if (times)
       ralledata_diff_gather_kernel<true><<<(unsigned)nt, kDiffBlobs, kWalkLdsBytes, stream>>>(
-          sa, na, sb, nb, k.part, k.keys_out, k.side, k.tile_count, rel, match, tm);
+          sa, na, sb, nb, k.part, k.st.hashes(), k.side, k.st.tile_count, rel, match, tm);
     else
-      ralledata_diff_gather_kernel<false><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(sa, na, sb, nb, k.part, k.keys_out,
-                                                                                 k.side, k.tile_count, rel, match, tm);
+      ralledata_diff_gather_kernel<false><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(
+          sa, na, sb, nb, k.part, k.st.hashes(), k.side, k.st.tile_count, rel, match, tm);
     tr(hipGetLastError());
   }
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, scan_bytes, k.tile_count, k.tile_base, nt + 1, stream));
-  if (tr.ok()) {
-    ralle_compact_kernel<kDiffBlobs><<<(unsigned)nt, kDiffBlobs, 0, stream>>>(k.part, k.keys_out, n, k.tile_base, nt, 0,
-                                                                             k.keys_in, k.idx_in);
-    tr(hipGetLastError());
-  }
-  if (tr.ok())
-    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
-                                          (const uint32_t*)k.idx_in, k.idx_out, n, 0, sort_bits, stream));
-  if (tr.ok()) {
-    ralle_mark_kernel<256><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(k.idx_out, n, nb, mark);
-    tr(hipGetLastError());
-  }
-  if (tr.ok())
-    tr(hipcub::DeviceScan::InclusiveScan(k.tmp, max_bytes, (const uint32_t*)mark, last_b, RalleMaxU32(), n, stream));
+  k.st.scan_tiles(tr, k.tmp, stream);
+  ralle_compact<kDiffBlobs>(tr, k.st, k.part, n, 0, stream);
+  k.st.sort(tr, k.tmp, stream);
+  ralle_mark<256>(tr, k.st, nb, stream);
+  k.st.max_scan(tr, k.tmp, k.st.mark(), last_b, stream);
   if (tr.ok()) {
     const uint64_t grid = (n + kDiffResolveBlock - 1) / kDiffResolveBlock;
-    const uint64_t mask = sort_mask(sort_bits);
+    const uint64_t mask = k.st.mask();
     if (times)
       ralledata_diff_resolve_kernel<true><<<(unsigned)grid, kDiffResolveBlock, 0, stream>>>(
-          sa, sb, nb, k.keys_out, k.idx_out, n, mask, last_b, k.side, rel, match, seen, work, tm);
+          sa, sb, nb, k.st.keys_out, k.st.idx_out, n, mask, last_b, k.side, rel, match, seen, work, tm);
     else
       ralledata_diff_resolve_kernel<false><<<(unsigned)grid, kDiffResolveBlock, 0, stream>>>(
-          sa, sb, nb, k.keys_out, k.idx_out, n, mask, last_b, k.side, rel, match, seen, work, tm);
+          sa, sb, nb, k.st.keys_out, k.st.idx_out, n, mask, last_b, k.side, rel, match, seen, work, tm);
     tr(hipGetLastError());
   }
   if (tr.ok()) {

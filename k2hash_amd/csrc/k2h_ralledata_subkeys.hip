@@ -24,9 +24,9 @@
 //            k2h_endwalk.h, as k2h_hash / k2h_second_hash compute them on the raw name bytes
 //            (no NUL is added: the name carries whatever NUL it was stored with); the lane
 //            lays the pair (hash, n + e) out for the sort behind the m participating blobs.
-//   sort     blobs at [0, n) and edges at [n, n + E) in one index space, sorted by the hash's
-//            low bits (sort_bits_for(n + E)); stable, so within a run of equal sorted bits the
-//            blobs come first, in stream order, then the edges.
+//   sort     blobs at [0, n) and edges at [n, n + E) in one index space, through the sort stage
+//            of k2h_sort_stage.h (tiles of the n blobs, n + E pairs); stable, so within a run of
+//            equal sorted bits the blobs come first, in stream order, then the edges.
 //   resolve  two mark kernels and two inclusive max-scans give every sorted position the
 //            nearest blob entry at or before it, and (scanned over the mirrored positions) the
 //            first position behind it that is no blob entry or starts another run.  One lane
@@ -305,11 +305,10 @@ struct CountCols {  // the count pass: a column of n + 1 counts, the counters, t
   size_t total;
 };
 struct JoinCols {  // the join, over N = n + E entries
-  uint64_t *keys_in, *keys_out;  // keys_out: first the blobs' hashes by index, then the sorted keys
-  uint32_t *idx_in, *idx_out, *bound_s;
+  SortStage<> st;
+  uint32_t* bound_s;
   Side* side;
   uint8_t* part;
-  uint64_t *tile_count, *tile_base;
   unsigned long long* counter;
   void* tmp;
   size_t total;
@@ -393,80 +392,55 @@ int launch_ralledata_subkeys(const void* blobs, uint64_t size, const uint64_t* b
 
   // the join, over N = n + E entries
   const uint64_t N = n + E;
-  size_t tile_bytes = 0, sort_bytes = 0, max_bytes = 0;
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, tile_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, nt + 1, stream));
-  const int sort_bits = sort_bits_for(N);
-  tr(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, N, 0, sort_bits, stream));
-  tr(hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, RalleMaxU32(), N,
-                                       stream));
+  SortStage<> st;
+  st.measure(tr, N, nt, stream);
+  st.measure_max_scan(tr, stream);
   if (!tr.ok()) return done();
-  size_t tmp_bytes = tile_bytes > sort_bytes ? tile_bytes : sort_bytes;
-  if (max_bytes > tmp_bytes) tmp_bytes = max_bytes;
   auto layout = [&](void* base) {
     Carver c(base);
     JoinCols k;
-    k.keys_in = c.take<uint64_t>(N);
-    k.keys_out = c.take<uint64_t>(N);
-    k.idx_in = c.take<uint32_t>(N);
-    k.idx_out = c.take<uint32_t>(N);
+    k.st = st.take(c);
     k.bound_s = c.take<uint32_t>(N);
     k.side = c.take<Side>(N);
     k.part = c.take<uint8_t>(n);
-    k.tile_count = c.take<uint64_t>(nt + 1);
-    k.tile_base = c.take<uint64_t>(nt + 1);
     k.counter = (unsigned long long*)c.bytes(kCounterBytes);
-    k.tmp = c.bytes(tmp_bytes);
+    k.tmp = c.bytes(st.tmp_bytes());
     k.total = c.total();
     return k;
   };
   if (const int rc = sc.reserve(layout(nullptr).total, stream, herr)) return rc;
   const JoinCols k = layout(sc.p);
-  // free once the sort has read them, its input columns: the first mark column takes the index
-  // column's place, its scan and the second mark column the two halves of the key column's
-  uint32_t* mark = k.idx_in;
-  uint32_t* last_b = (uint32_t*)k.keys_in;
-  uint32_t* mark_r = last_b + N;
+  // the first mark column's scan and the second mark column stand in the stage's input columns
+  uint32_t* const last_b = k.st.scanned();
+  uint32_t* const mark_r = k.st.second();
 
-  tr(hipMemsetAsync(k.tile_count + nt, 0, 8, stream));
+  k.st.clear(tr, stream);
   tr(hipMemsetAsync(k.counter, 0, kCounterBytes, stream));
   if (tr.ok()) {
-    subkeys_emit_kernel<<<(unsigned)nt, kSkBlobs, kWalkLdsBytes, stream>>>(s, n, edge_off, E, k.part, k.keys_out,
-                                                                           k.side, k.tile_count, rep);
+    subkeys_emit_kernel<<<(unsigned)nt, kSkBlobs, kWalkLdsBytes, stream>>>(s, n, edge_off, E, k.part, k.st.hashes(),
+                                                                           k.side, k.st.tile_count, rep);
     tr(hipGetLastError());
   }
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, tile_bytes, k.tile_count, k.tile_base, nt + 1, stream));
-  if (tr.ok()) {
-    ralle_compact_kernel<kSkBlobs><<<(unsigned)nt, kSkBlobs, 0, stream>>>(k.part, k.keys_out, n, k.tile_base, nt, E,
-                                                                          k.keys_in, k.idx_in);
-    tr(hipGetLastError());
-  }
+  k.st.scan_tiles(tr, k.tmp, stream);
+  ralle_compact<kSkBlobs>(tr, k.st, k.part, n, E, stream);
   if (tr.ok() && E) {
     subkeys_hash_kernel<<<(unsigned)((E + kSkBlock - 1) / kSkBlock), kSkBlock, 0, stream>>>(
-        s.blobs, n, E, k.side, k.tile_base, nt, k.keys_in, k.idx_in, make_spad(seed));
+        s.blobs, n, E, k.side, k.st.tile_base, nt, k.st.keys_in, k.st.idx_in, make_spad(seed));
     tr(hipGetLastError());
   }
-  if (tr.ok())
-    tr(hipcub::DeviceRadixSort::SortPairs(k.tmp, sort_bytes, (const uint64_t*)k.keys_in, k.keys_out,
-                                          (const uint32_t*)k.idx_in, k.idx_out, N, 0, sort_bits, stream));
+  k.st.sort(tr, k.tmp, stream);
   const unsigned grid = (unsigned)((N + kSkBlock - 1) / kSkBlock);
-  const uint64_t mask = sort_mask(sort_bits);
+  const uint64_t mask = k.st.mask();
+  ralle_mark<kSkBlock>(tr, k.st, n, stream);
   if (tr.ok()) {
-    ralle_mark_kernel<kSkBlock><<<grid, kSkBlock, 0, stream>>>(k.idx_out, N, n, mark);
+    subkeys_bound_kernel<<<grid, kSkBlock, 0, stream>>>(k.st.keys_out, k.st.idx_out, N, n, mask, mark_r);
     tr(hipGetLastError());
   }
+  k.st.max_scan(tr, k.tmp, k.st.mark(), last_b, stream);
+  k.st.max_scan(tr, k.tmp, mark_r, k.bound_s, stream);
   if (tr.ok()) {
-    subkeys_bound_kernel<<<grid, kSkBlock, 0, stream>>>(k.keys_out, k.idx_out, N, n, mask, mark_r);
-    tr(hipGetLastError());
-  }
-  if (tr.ok())
-    tr(hipcub::DeviceScan::InclusiveScan(k.tmp, max_bytes, (const uint32_t*)mark, last_b, RalleMaxU32(), N, stream));
-  if (tr.ok())
-    tr(hipcub::DeviceScan::InclusiveScan(k.tmp, max_bytes, (const uint32_t*)mark_r, k.bound_s, RalleMaxU32(), N,
-                                         stream));
-  if (tr.ok()) {
-    subkeys_resolve_kernel<<<grid, kSkBlock, 0, stream>>>(s.blobs, n, k.keys_out, k.idx_out, N, mask, last_b, k.bound_s,
-                                                         k.side, rep, child, k.counter);
+    subkeys_resolve_kernel<<<grid, kSkBlock, 0, stream>>>(s.blobs, n, k.st.keys_out, k.st.idx_out, N, mask, last_b,
+                                                         k.bound_s, k.side, rep, child, k.counter);
     tr(hipGetLastError());
   }
   if (tr.ok()) tr(hipMemcpyAsync(host, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));

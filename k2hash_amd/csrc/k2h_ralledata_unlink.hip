@@ -18,7 +18,7 @@
 //            pass of k2h_ralledata_subkeys.hip over again and starts from its launch shape
 //            (kWalkLdsBytes, two waves per SIMD); without a drop mask nothing of the stream is
 //            read and the kernel runs at full occupancy.
-//   scan     two exclusive sums: the sizes into places, the kept flags into ranks.  The counts
+//   scan     PlaceRank (k2h_sort_stage.h): the sizes into places, the kept flags into ranks.  The counts
 //            come back to the host (the one synchronisation).
 //   copy     the select copy kernel's scheme over the places (k2h_ralle_copy.h): a tile of
 //            256 blobs writes its destination span as aligned 16-byte pieces, one unaligned
@@ -46,7 +46,6 @@
 // blob whose range lies inside [0, edge_off[n]].  Nothing of a blob that is not emitted is
 // read; of an emitted blob without PART, or with BAD, in sk_flags nothing is interpreted.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include <mutex>
@@ -252,9 +251,8 @@ int launch_ralledata_unlink(const void* blobs, uint64_t size, const uint64_t* bl
     return !tr.ok() ? K2H_AMD_EHIP : rc;
   };
   UlScratch* const scp = g_ul.current(tr);
-  size_t b8 = 0, b4 = 0;
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b8, (uint64_t*)nullptr, (uint64_t*)nullptr, n + 1, stream));
-  tr(hipcub::DeviceScan::ExclusiveSum(nullptr, b4, (uint32_t*)nullptr, (uint32_t*)nullptr, n + 1, stream));
+  PlaceRank<> pr;
+  pr.measure(tr, n, stream);
   if (!tr.ok()) return done(K2H_AMD_OK);
   UlScratch& sc = *scp;
   std::lock_guard<std::mutex> lk(sc.mu);
@@ -268,7 +266,7 @@ int launch_ralledata_unlink(const void* blobs, uint64_t size, const uint64_t* bl
     k.rank = c.take<uint32_t>(n + 1);
     k.chg = c.take<uint8_t>(n);
     k.counter = (unsigned long long*)c.bytes(kCounterBytes);
-    k.tmp = c.bytes(b8 > b4 ? b8 : b4);
+    k.tmp = c.bytes(pr.tmp_bytes());
     k.total = c.total();
     return k;
   };
@@ -282,8 +280,7 @@ int launch_ralledata_unlink(const void* blobs, uint64_t size, const uint64_t* bl
         s, n, k.place, k.rank, k.chg, changed, k.counter);
     tr(hipGetLastError());
   }
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b8, k.place, k.place, n + 1, stream));
-  if (tr.ok()) tr(hipcub::DeviceScan::ExclusiveSum(k.tmp, b4, k.rank, k.rank, n + 1, stream));
+  pr.scan(tr, k.tmp, k.place, k.rank, stream);
   if (tr.ok()) tr(hipMemcpyAsync(host, k.counter, kCounterBytes, hipMemcpyDeviceToHost, stream));
   if (tr.ok()) tr(sc.mark_done(stream));
   if (tr.ok()) tr(hipStreamSynchronize(stream));
