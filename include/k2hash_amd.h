@@ -1025,6 +1025,121 @@ int k2h_amd_ralledata_delta(const void* a_blobs, uint64_t a_size, const uint64_t
                             uint64_t nb, const uint8_t* b_consider, const uint8_t* seen, void* out, uint64_t out_cap,
                             uint64_t* slot_off, uint8_t* made, uint64_t* counts, void* stream);
 
+/* 4e. Keys looked up in a held stream: index, find and fetch.  Every call above feeds, routes,
+ * rewrites or compares a stream; these three answer what it holds for a key.  Together they are
+ * K2HShm::Get(const unsigned char*, size_t, unsigned char**, bool checkattr, ...)
+ * (lib/k2hshm.cc:1857-1938) for a batch of keys, answered from a stream in device memory with
+ * no table: the element is reached as GetElement reaches it and as SetElementByBinArray does
+ * (lib/k2hshmdirect.cc:373-378) -- K2H_HASH_FUNC / K2H_2ND_HASH_FUNC of the key, then hash,
+ * subhash, key length, key bytes, the identity of section 4b'.  The held side is sorted once, by
+ * _index, and probed many times, by _find; _fetch is the inverse of k2h_amd_build_ralledata for
+ * one segment.  All pointers are device pointers unless marked host; every call runs on `stream`.
+ *
+ * k2h_amd_ralledata_index.  Participants, as in section 4b': consider NULL or consider[i] != 0,
+ * a span inside [0, size) of at least 80 bytes, a header that is not EMPTY, NO_KEY or BAD_RANGE.
+ * The index is opaque, caller-owned device memory of k2h_amd_ralledata_index_size(n) bytes (host
+ * arithmetic only; about 44 bytes per blob: the hashes sorted on their low bits, the blob of each
+ * sorted position, a 32-byte record per blob, and a 256-byte header that is written last) at a
+ * 256-byte aligned address.  It is library output and is trusted by _find, as a stream's stored
+ * hashes are trusted by section 4b'; it is valid for exactly the (blobs, size, blob_off, n) bytes
+ * it was built from.  *participants (host, may be NULL) receives their number: given, `stream` is
+ * synchronised once to return it; NULL, nothing waits for the device.  n == 0 is valid and gives
+ * an index in which nothing is found.
+ *   K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ *   blobs or blob_off NULL with n > 0; index NULL; index_cap below the size function's value;
+ *   index not 256-byte aligned; n > 2^32 - 2 (indices are sorted as 32-bit values).
+ *   Cost: dedup's gather, compact and sort, and no resolve.  Temporary device memory, kept per
+ *   device between calls: 13 bytes per blob, the tile counts and the sort's own.
+ *
+ * k2h_amd_ralledata_find.  The m queries are a CSR column: query i = keys[key_off[i],
+ * key_off[i+1]), m + 1 offsets.  Query i takes part when key_off[i] <= key_off[i+1] <= key_bytes
+ * and it has at least one byte; with K2H_AMD_FLAG_CSTR a query of any length takes part and
+ * stands for its bytes plus one NUL that the buffer does not hold, as Get(const char*) passes
+ * strlen + 1 (every blob of the import route stores such keys).  Its hashes are h1[i] / h2[i] or,
+ * with both NULL, what k2h_amd_hash_csr gives for it under `flags`; K2H_AMD_FLAG_STD_FNV is legal
+ * only then, _CSTR either way.  Its lookup length L is its length, plus 1 with _CSTR.  Each query
+ * is judged alone: the offsets need not be monotone from query to query.
+ *   The match is the LAST participant of the stream (the choice of section 4b''''''s match) with
+ * stored hash == h1, stored subhash == h2, key_length == L and the query's key bytes -- with
+ * _CSTR the query's bytes and a final byte of 0.  A blob whose stored hashes are not those of its
+ * key is never matched, as Get would never find it.
+ *   match[i]   (m, may be NULL) the blob index, or ~0.
+ *   status[i]  (m, required) K2H_AMD_FIND_* bits: _PART the query takes part; _FOUND a blob
+ *              matched; _ATTRS the matched blob has attrs_length != 0; _EXPIRED only when `now`
+ *              (host, may be NULL, read before the call returns) is given: the matched blob's attrs
+ *              give an expire earlier than *now, the IsExpire rule of section 4b'''' -- only the
+ *              attrs of matched blobs are walked.  Get(..., checkattr = true) returns a value
+ *              exactly for _FOUND without _EXPIRED, up to the history marker and value
+ *              decryption, which are not judged: _ATTRS lets a caller route such keys to the CPU.
+ *              _BAD_INDEX: the index header's magic, n or size disagree with the arguments; then
+ *              every query gets exactly this byte, match is ~0, hit stays 0 and nothing behind
+ *              the header is read.
+ *   hit[j]     (n, may be NULL) all n entries are written: 0 by one memset on `stream`, then 1 for
+ *              every blob that is some query's match.  On a stream with one blob per identity (a
+ *              dump, or the survivors of section 4b') keep = !hit followed by
+ *              k2h_amd_ralledata_select is a batch Remove(key).  With several copies of an
+ *              identity only the last copy is marked.
+ *   counts     (host, 3 entries, may be NULL) the queries that take part, found, expired.  Given,
+ *              `stream` is synchronised once to return them; NULL, nothing waits for the device.
+ *   m == 0: K2H_AMD_OK, counts zeroed, hit zeroed by its memset, no kernel.  n == 0: an ordinary
+ *   call in which nothing is found.
+ *   K2H_AMD_EINVAL (host side, each with its own message): status NULL with m > 0; keys NULL with
+ *   key_bytes > 0; key_off NULL with m > 0; index NULL; blobs or blob_off NULL with n > 0; exactly
+ *   one of h1 / h2 NULL; unknown flag bits; _STD_FNV with the hashes given; n > 2^32 - 2.
+ *   Memory rule: no byte outside [0, key_bytes) of keys or [0, size) of the stream is read, except
+ *   within the aligned 16 bytes that hold a valid byte; nothing of a query that takes no part;
+ *   all absolute offsets are 64-bit.
+ *   Cost: one lane per query; about ceil(log2 P) dependent loads (P the participants) and the
+ *   walk back through the run of the query's sorted hash bits -- one entry, now and then two.  r
+ *   distinct identities that share the sorted bits cost O(r) per lane: the crafted-stream case of
+ *   section 4b'.  Hashes not passed are computed one lane per query first.  Temporary device
+ *   memory, kept per device between calls: 4 KiB of counters, and 16 bytes per query when the
+ *   hashes are computed.
+ *
+ * k2h_amd_ralledata_fetch.  Slot i yields the chosen segment (K2H_AMD_SEG_*) of blob which[i], in
+ * slot order, packed back to back: out[out_off[i], out_off[i+1]), out_off has m + 1 entries and
+ * starts at 0.  take (m, or NULL: every slot).  A slot yields 0 bytes when take[i] == 0 or
+ * which[i] == ~0, and 0 bytes with bad[i] = 1 (bad: m, may be NULL) when which[i] >= n, the
+ * blob's span is bad or shorter than 80 bytes, or the segment's [pos, pos + length) is not inside
+ * [0, blob length) -- tested without forming a sum that can wrap; the pos of a length-0 segment
+ * is ignored.  No other header test is made: a blob's segments may be permuted, gapped or
+ * overlapping, as section 5c accepts.  Repeated indices are legal: the blob is copied twice.
+ *   out == NULL: count only; *total (host, required), and out_off and bad if given, are filled.
+ *   *total > out_cap: K2H_AMD_EINVAL with total set and nothing written to out.  `stream` is
+ *   synchronised exactly once per call, to return total, then the bytes are copied asynchronously
+ *   on `stream`; with m == 0 nothing waits for the device.
+ *   K2H_AMD_EINVAL (host side, each with its own message): total NULL; which NULL with m > 0;
+ *   blobs or blob_off NULL with n > 0 and m > 0; an unknown segment; out given without out_off.
+ *   Memory rule: that of _find for the stream; only the segments' own bytes are read, and nothing
+ *   of out at or beyond *total is written.
+ *   Cost: a 16-byte header read per slot, one scan over m + 1 entries, and a copy pass: 16 lanes
+ *   per slot in 16-byte pieces, a slot of 4 KiB or more by a whole block.  Temporary device
+ *   memory, kept per device between calls: 16 bytes per slot plus the scan's own.
+ *
+ * Parity: libk2hash is not built by this project's tests, so parity with Get is a restatement
+ * against the Python model of tests/ralle_find_model.py, whose lookup is shown to agree with
+ * "feed the blobs in order, the last one wins". */
+#define K2H_AMD_FIND_PART 0x01u
+#define K2H_AMD_FIND_FOUND 0x02u
+#define K2H_AMD_FIND_ATTRS 0x04u
+#define K2H_AMD_FIND_EXPIRED 0x08u
+#define K2H_AMD_FIND_BAD_INDEX 0x80u
+#define K2H_AMD_SEG_KEY 0u
+#define K2H_AMD_SEG_VAL 1u
+#define K2H_AMD_SEG_SKEY 2u
+#define K2H_AMD_SEG_ATTRS 3u
+uint64_t k2h_amd_ralledata_index_size(uint64_t n);
+int k2h_amd_ralledata_index(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                            const uint8_t* consider, void* index, uint64_t index_cap, uint64_t* participants,
+                            void* stream);
+int k2h_amd_ralledata_find(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const void* index,
+                           const void* keys, uint64_t key_bytes, const uint64_t* key_off, uint64_t m,
+                           const uint64_t* h1, const uint64_t* h2, uint32_t flags, const k2h_amd_timespec* now,
+                           uint64_t* match, uint8_t* status, uint8_t* hit, uint64_t* counts, void* stream);
+int k2h_amd_ralledata_fetch(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                            const uint64_t* which, uint64_t m, const uint8_t* take, uint32_t segment, void* out,
+                            uint64_t out_cap, uint64_t* out_off, uint8_t* bad, uint64_t* total, void* stream);
+
 /* ---------------------------------------------------------------------------
  * 5. Bulk key streams: keys anywhere in a buffer, and k2hash archives.
  *

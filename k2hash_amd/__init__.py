@@ -23,6 +23,9 @@ and (2) a batch C ABI backed by hand-written gfx950 HIP kernels (section 2).
              (apply_log, apply_records)
   delta      the inverse: from a held and a new blob stream to the transaction log that turns
              the one into the other (delta_log, delta_records)
+  find       keys looked up in a held blob stream: the stream indexed once, a batch of keys found
+             through the index (Get without a table), and one segment of a list of blobs fetched
+             as a CSR column (index_stream, find_keys, fetch_segments, get_values)
   shard      multi-GPU partitioning and the RCCL gather of hashes
 """
 from .hashfunc import (K2H_2ND_HASH_FUNC, K2H_HASH_FUNC, K2H_HASH_VER_FUNC, K2HashDynLib, k2h_hash,
@@ -32,6 +35,7 @@ from .batch import (bucket_index, hash_csr, hash_csr_host, hash_csr_index, hash_
 from .apply import Applied, apply_log, apply_records
 from .archive import compact_device, fold_device
 from .delta import Delta, delta_log, delta_records
+from .find import Found, StreamIndex, fetch_segments, find_keys, get_values, index_stream
 from .ralledata import (Diff, HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
                         dedup_ralledata, diff_ralledata, import_file_to_archive, import_file_to_ralledata, import_to_ralledata, make_hash_range, partition_ralledata,
                         ralledata_to_archive, route_ralledata, select_ralledata)
@@ -49,4 +53,5 @@ __all__ = [
     "subkey_edges", "reach_subkeys", "subtree_ralledata", "SubkeyEdges", "Reach",
     "drop_mask", "unlink_subkeys", "prune_ralledata", "Unlinked", "apply_log", "apply_records", "Applied",
     "delta_log", "delta_records", "Delta",
+    "index_stream", "find_keys", "fetch_segments", "get_values", "StreamIndex", "Found",
 ]

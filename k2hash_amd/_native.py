@@ -88,6 +88,9 @@ K2H_AMD_UNLINK_REWRITTEN, K2H_AMD_UNLINK_EMPTIED, K2H_AMD_UNLINK_KEY_ONLY = 0x1,
 K2H_AMD_APPLY_TOUCHED, K2H_AMD_APPLY_SUPERSEDED, K2H_AMD_APPLY_LEFT_OUT = 1, 2, 3
 K2H_AMD_DELTA_SET_ALL, K2H_AMD_DELTA_REPLACE_VAL, K2H_AMD_DELTA_REPLACE_SKEY = 0x01, 0x02, 0x04
 K2H_AMD_DELTA_REPLACE_ATTRS, K2H_AMD_DELTA_DEL_KEY = 0x08, 0x10
+K2H_AMD_FIND_PART, K2H_AMD_FIND_FOUND, K2H_AMD_FIND_ATTRS, K2H_AMD_FIND_EXPIRED = 0x01, 0x02, 0x04, 0x08
+K2H_AMD_FIND_BAD_INDEX = 0x80
+K2H_AMD_SEG_KEY, K2H_AMD_SEG_VAL, K2H_AMD_SEG_SKEY, K2H_AMD_SEG_ATTRS = 0, 1, 2, 3
 
 _twp = ctypes.POINTER(TimeWindowStruct)
 _dtp = ctypes.POINTER(DiffTimes)
@@ -130,6 +133,12 @@ SIGNATURES = {
     "k2h_amd_archive_ralledata": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, _u64p, ctypes.c_uint32, _p]),
     "k2h_amd_ralledata_archive": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64p, _u64p, _p]),
     "k2h_amd_ralledata_delta": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _p, _p, _p, _u64, _p, _p,
+                                               _u64p, _p]),
+    "k2h_amd_ralledata_index_size": (_u64, [_u64]),
+    "k2h_amd_ralledata_index": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _u64p, _p]),
+    "k2h_amd_ralledata_find": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _p, _p, ctypes.c_uint32, _tsp,
+                                              _p, _p, _p, _u64p, _p]),
+    "k2h_amd_ralledata_fetch": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _u64, _p, ctypes.c_uint32, _p, _u64, _p, _p,
                                                _u64p, _p]),
     "k2h_amd_hash_ranges": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, ctypes.c_uint32, _p]),
     "k2h_amd_archive_scan": (ctypes.c_int, [_p, _u64, _p, _u64, _p]),

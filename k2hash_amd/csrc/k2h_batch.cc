@@ -1224,6 +1224,88 @@ __attribute__((visibility("default"))) int k2h_amd_ralledata_delta(
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_delta", e);
 }
 
+// Section 4e: keys looked up in a held stream.  Judged on the host like the ones above.
+__attribute__((visibility("default"))) uint64_t k2h_amd_ralledata_index_size(uint64_t n) {
+  return k2h::ralledata_index_bytes(n);
+}
+
+__attribute__((visibility("default"))) int k2h_amd_ralledata_index(const void* blobs, uint64_t size,
+                                                                   const uint64_t* blob_off, uint64_t n,
+                                                                   const uint8_t* consider, void* index,
+                                                                   uint64_t index_cap, uint64_t* participants,
+                                                                   void* stream) {
+  if (participants) *participants = 0;
+  if (n && !blobs) return fail(K2H_AMD_EINVAL, "ralledata_index: NULL blobs");
+  if (n && !blob_off) return fail(K2H_AMD_EINVAL, "ralledata_index: NULL blob_off");
+  if (!index) return fail(K2H_AMD_EINVAL, "ralledata_index: NULL index");
+  if (n > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL, "ralledata_index: more than 2^32 - 2 blobs (indices are sorted as 32-bit values)");
+  if (index_cap < k2h::ralledata_index_bytes(n)) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "ralledata_index: index_cap %llu is below k2h_amd_ralledata_index_size(n) = %llu",
+             (unsigned long long)index_cap, (unsigned long long)k2h::ralledata_index_bytes(n));
+    return fail(K2H_AMD_EINVAL, msg);
+  }
+  if ((uintptr_t)index & 255u) return fail(K2H_AMD_EINVAL, "ralledata_index: index is not 256-byte aligned");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_ralledata_index(blobs, size, blob_off, n, consider, index, participants, (hipStream_t)stream, &e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_index", e);
+}
+
+__attribute__((visibility("default"))) int k2h_amd_ralledata_find(
+    const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const void* index, const void* keys,
+    uint64_t key_bytes, const uint64_t* key_off, uint64_t m, const uint64_t* h1, const uint64_t* h2, uint32_t flags,
+    const k2h_amd_timespec* now, uint64_t* match, uint8_t* status, uint8_t* hit, uint64_t* counts, void* stream) {
+  if (counts) counts[0] = counts[1] = counts[2] = 0;
+  if (m && !status) return fail(K2H_AMD_EINVAL, "ralledata_find: NULL status");
+  if (key_bytes && !keys) return fail(K2H_AMD_EINVAL, "ralledata_find: NULL keys");
+  if (m && !key_off) return fail(K2H_AMD_EINVAL, "ralledata_find: NULL key_off");
+  if (!index) return fail(K2H_AMD_EINVAL, "ralledata_find: NULL index");
+  if (n && !blobs) return fail(K2H_AMD_EINVAL, "ralledata_find: NULL blobs");
+  if (n && !blob_off) return fail(K2H_AMD_EINVAL, "ralledata_find: NULL blob_off");
+  if (!h1 != !h2) return fail(K2H_AMD_EINVAL, "ralledata_find: h1 and h2 go together, both given or both NULL");
+  if (flags & ~(K2H_AMD_FLAG_STD_FNV | K2H_AMD_FLAG_CSTR)) return fail(K2H_AMD_EINVAL, "ralledata_find: unknown flags");
+  if ((flags & K2H_AMD_FLAG_STD_FNV) && h1)
+    return fail(K2H_AMD_EINVAL, "ralledata_find: K2H_AMD_FLAG_STD_FNV is legal only when h1 and h2 are NULL");
+  if (n > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL, "ralledata_find: more than 2^32 - 2 blobs (indices are sorted as 32-bit values)");
+  if (m == 0 && !(hit && n)) return K2H_AMD_OK;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  if (m == 0) {  // no query: no blob is a match
+    e = hipMemsetAsync(hit, 0, n, (hipStream_t)stream);
+    return e == hipSuccess ? K2H_AMD_OK : fail(K2H_AMD_EHIP, "ralledata_find: hipMemsetAsync", e);
+  }
+  int rc = k2h::launch_ralledata_find(blobs, size, blob_off, n, index, keys, key_bytes, key_off, m, h1, h2,
+                                      seed_for(flags), (flags & K2H_AMD_FLAG_CSTR) != 0, now, match, status, hit, counts,
+                                      (hipStream_t)stream, &e);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_find", e);
+}
+
+__attribute__((visibility("default"))) int k2h_amd_ralledata_fetch(const void* blobs, uint64_t size,
+                                                                   const uint64_t* blob_off, uint64_t n,
+                                                                   const uint64_t* which, uint64_t m,
+                                                                   const uint8_t* take, uint32_t segment, void* out,
+                                                                   uint64_t out_cap, uint64_t* out_off, uint8_t* bad,
+                                                                   uint64_t* total, void* stream) {
+  if (!total) return fail(K2H_AMD_EINVAL, "ralledata_fetch: NULL total");
+  *total = 0;
+  if (m && !which) return fail(K2H_AMD_EINVAL, "ralledata_fetch: NULL which");
+  if (m && n && !blobs) return fail(K2H_AMD_EINVAL, "ralledata_fetch: NULL blobs");
+  if (m && n && !blob_off) return fail(K2H_AMD_EINVAL, "ralledata_fetch: NULL blob_off");
+  if (segment > K2H_AMD_SEG_ATTRS) return fail(K2H_AMD_EINVAL, "ralledata_fetch: unknown segment");
+  if (out && !out_off) return fail(K2H_AMD_EINVAL, "ralledata_fetch: out given without out_off");
+  if (m == 0 && !out_off) return K2H_AMD_OK;
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  if (m == 0) return clear_word(out_off, stream, "ralledata_fetch: hipMemsetAsync");  // no slot
+  int rc = k2h::launch_ralledata_fetch(blobs, size, blob_off, n, which, m, take, segment, out, out_cap, out_off, bad,
+                                       total, (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EINVAL) return exceeds_cap("ralledata_fetch", "segments", *total, out_cap);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_ralledata_fetch", e);
+}
+
 __attribute__((visibility("default"))) const char* k2h_amd_version(void) {
   return "k2hash_amd 0.1 (FNV-1A BUILTIN, gfx950 HIP batch kernels)";
 }

@@ -214,6 +214,27 @@ int launch_ralledata_delta(const void* a_blobs, uint64_t a_size, const uint64_t*
                            const uint8_t* b_consider, const uint8_t* seen, void* out, uint64_t out_cap, uint64_t* slot_off,
                            uint8_t* made, uint64_t* counts, hipStream_t stream, hipError_t* herr);
 
+// Keys looked up in a held stream (k2h_ralledata_find.hip).  All three return a K2H_AMD_* code (the
+// HIP error in *herr); n <= 2^32 - 2.  ralledata_index_bytes is host arithmetic alone.  _index
+// (index: at least ralledata_index_bytes(n), 256-byte aligned) synchronises the stream once when
+// participants != NULL, _find (m >= 1; h1 and h2 both given or both NULL, then hashed with `seed`;
+// now a host pointer, read before the return) once when counts != NULL, _fetch (m >= 1) always
+// once, to return *total; out == NULL: sizes only; *total > out_cap: K2H_AMD_EINVAL with nothing
+// written to out.
+uint64_t ralledata_index_bytes(uint64_t n);
+int launch_ralledata_index(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                           const uint8_t* consider, void* index, uint64_t* participants, hipStream_t stream,
+                           hipError_t* herr);
+int launch_ralledata_find(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n, const void* index,
+                          const void* keys, uint64_t key_bytes, const uint64_t* key_off, uint64_t m,
+                          const uint64_t* h1, const uint64_t* h2, uint64_t seed, bool cstr,
+                          const k2h_amd_timespec* now, uint64_t* match, uint8_t* status, uint8_t* hit,
+                          uint64_t* counts, hipStream_t stream, hipError_t* herr);
+int launch_ralledata_fetch(const void* blobs, uint64_t size, const uint64_t* blob_off, uint64_t n,
+                           const uint64_t* which, uint64_t m, const uint8_t* take, uint32_t segment, void* out,
+                           uint64_t out_cap, uint64_t* out_off, uint8_t* bad, uint64_t* total, hipStream_t stream,
+                           hipError_t* herr);
+
 // Keys at arbitrary (start, length) ranges (k2h_ranges.hip); cstr: hash key + NUL.
 hipError_t launch_ranges(const void* base, const uint64_t* starts, const uint64_t* lens, uint64_t n, uint64_t seed,
                          bool cstr, uint64_t* h1, uint64_t* h2, hipStream_t stream);
