@@ -1,6 +1,7 @@
-"""Helper for tests/test_scale_streams.py and tests/test_sort_regimes.py (not a test module, not a
-conftest): streams of a million blobs or records, built with numpy, and what the sort-based calls
-must answer on them, derived from the columns the generator wrote.
+"""Helper for tests/test_scale_streams.py, tests/test_sort_regimes.py and tests/test_find_regimes.py
+(not a test module, not a conftest): streams of a million blobs or records, built with numpy, and
+what the sort-based calls must answer on them, derived from the columns the generator wrote; for
+k2h_amd_ralledata_find also the queries (find_queries) and their answer (find_expect).
 
 The per-blob builders (dm.blobs_of, sm.blobs_with_lists, archive_fold_model.scom_record) give one
 template per kind of blob or record; the template is tiled and the key bytes, the value, the names
@@ -346,6 +347,99 @@ def ralle_holds(c, part):
         not_considered=int((c.consider == 0).sum()), no_key=int((c.bad == 1).sum()), key_past=int((c.bad == 2).sum()),
         non_participants_with_a_live_identity=int(live.sum()), non_participants=int(notpart.size),
         attrs=int(c.att[idx].sum()))
+
+
+# --------------------------------------------------------------------------------------- find
+Q_PICK, Q_ROLE, Q_FRESH, Q_NEAR, Q_EMPTY = range(5)     # why a query is there
+FIND_ROLES = ("hot", "xor", "same", "subflip", "ones", "exact")
+FIND_PART, FIND_FOUND, FIND_ATTRS, FIND_EXPIRED = 0x01, 0x02, 0x04, 0x08   # include/k2hash_amd.h section 4e, restated
+M_LARGE = (1 << 18) + 77     # queries over the N_LARGE stream: no multiple of 256, 4,098 waves
+FIND_SEEDS = (1, 5)          # the N_LARGE find tests' columns (the dedup stream's) and queries
+
+
+def find_queries(oracle, c, m, seed):
+    """m queries over the columns c, in an order unrelated to the stream: q.key (m x KW key rows),
+    q.klen, the CSR q.bytes and q.key_off (uint64 m + 1), and two hash pairs per query, q.stored
+    (the picked blob's stored hash and subhash) and q.true (true_hashes of the query's bytes).
+    q.kind says why a query is there and q.pick which blob it was taken from (-1: none):
+
+    * Q_PICK: a blob picked uniformly, participant or not;
+    * Q_ROLE: every blob of the roles hot, xor, same, subflip, ones and exact;
+    * Q_FRESH: a key no blob has, stored == true;
+    * Q_NEAR: a picked participant's stored hashes over its key with one byte changed, byte 0 (chunk 0
+      of the compare, under its lead mask) for the first half, the last byte for the second -- by bits
+      the role `same` does not use, so that no blob has the changed key;
+    * Q_EMPTY: key_off[i] == key_off[i + 1], which takes no part."""
+    rng = np.random.default_rng([seed, 11])
+    n = c.n
+    roles = np.concatenate([c.roles[name] for name in FIND_ROLES])
+    n_empty, n_fresh, n_near = min(100, m // 8), m // 32, m // 32 // 2 * 2
+    n_pick = m - roles.size - n_empty - n_fresh - n_near
+    assert n_pick > m // 2, "m is too small for the roles"
+    pick = np.concatenate([rng.integers(0, n, n_pick), roles])
+    idx = np.flatnonzero(participants(c, False))
+    near = idx[rng.integers(0, idx.size, n_near)]
+    fresh_long = rng.random(n_fresh) < 0.5
+    fresh = fresh_keys(n + np.arange(n_fresh), fresh_long)
+    near_key = c.key[near].copy()
+    half = n_near // 2
+    near_key[:half, 0] ^= 0x40
+    near_key[np.arange(half, n_near), c.klen[near[half:]] - 1] ^= 0x02
+    q = types.SimpleNamespace(m=m)
+    q.key = np.concatenate([c.key[pick], fresh, near_key, np.zeros((n_empty, KW), np.uint8)])
+    q.klen = np.concatenate([c.klen[pick], np.where(fresh_long, KLEN[1], KLEN[0]), c.klen[near], np.zeros(n_empty, np.int64)])
+    q.kind = np.repeat([Q_PICK, Q_ROLE, Q_FRESH, Q_NEAR, Q_EMPTY], [n_pick, roles.size, n_fresh, n_near, n_empty])
+    q.pick = np.concatenate([pick, np.full(n_fresh, -1), near, np.full(n_empty, -1)])
+    order = rng.permutation(m)
+    q.key, q.klen, q.kind, q.pick = q.key[order], q.klen[order], q.kind[order], q.pick[order]
+    full = np.flatnonzero(q.klen > 0)
+    h, s = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+    h[full], s[full] = true_hashes(oracle, q.key[full], q.klen[full])
+    q.true = (h, s)
+    from_blob = q.pick >= 0
+    q.stored = (np.where(from_blob, c.hash[q.pick], h), np.where(from_blob, c.sub[q.pick], s))
+    q.key_off = np.zeros(m + 1, np.uint64)
+    q.key_off[1:] = np.cumsum(q.klen)
+    q.bytes = q.key[np.arange(KW)[None, :] < q.klen[:, None]]
+    return q
+
+
+def find_expect(c, part, q, hashes, now=None, later="last"):
+    """(match uint64 m, status uint8 m, hit uint8 n, counts [part, found, expired]) of the queries q
+    under the hash pair `hashes` (q.stored or q.true) against the participants `part`: the LAST
+    participant with the query's hash, subhash, key length and key bytes.  later="first": the
+    EARLIEST copy instead -- what an unstable sort, or a walk in the wrong direction, could leave.
+
+    EXPIRED is ralle_times_model.is_expire over the attrs segments the generator can write, one per
+    value of c.ab.  None of them parses to an expire entry (six bytes: shorter than the count), so no
+    match expires and counts[2] == 0 with `now` given; expiry itself is pinned by the planted stream
+    of tests/test_ralledata_find.py, not at scale."""
+    import ralle_times_model as tm
+    idx = np.flatnonzero(part)
+    full = np.flatnonzero(q.klen > 0)
+    kw = np.ascontiguousarray(q.key[full]).view("<u8")
+    qcols = [hashes[0][full], hashes[1][full], q.klen[full], kw[:, 0], kw[:, 1], kw[:, 2]]
+    j = join_last(ident_cols(c, idx), idx if later == "last" else c.n - idx, qcols)
+    found = j >= 0
+    if later != "last":
+        j = np.where(found, c.n - j, j)
+    match, status, hit = np.full(q.m, NONE, np.uint64), np.zeros(q.m, np.uint8), np.zeros(c.n, np.uint8)
+    status[full] = FIND_PART
+    at, j = full[found], j[found]
+    match[at] = j.astype(np.uint64)
+    hit[j] = 1
+    expires = np.array([now is not None and tm.is_expire(bytes([ab]) + ATTRS[1:], now) for ab in range(4)])
+    status[at] |= (FIND_FOUND | FIND_ATTRS * c.att[j] | FIND_EXPIRED * (c.att[j] & expires[c.ab[j]])).astype(np.uint8)
+    return match, status, hit, [int(full.size), int(at.size), int((status & FIND_EXPIRED != 0).sum())]
+
+
+def shared_sorted_bits(c, part, bits):
+    """Neighbours in the stable order of the participants by their stored hash's low `bits` bits that
+    share those bits under different hashes: the entries the backward walk steps over by hash alone."""
+    h = c.hash[np.flatnonzero(part)]
+    mask = np.uint64((1 << bits) - 1)
+    s = h[np.argsort(h & mask, kind="stable")]
+    return int((((s[1:] ^ s[:-1]) & mask == 0) & (s[1:] != s[:-1])).sum())
 
 
 # --------------------------------------------------------------------------------------- diff

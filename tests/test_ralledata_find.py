@@ -13,6 +13,9 @@ The planted stream is deterministic and every blob in it is there for one reason
   part under another identity (wrong stored hash), so the earlier copy is the match;
 * exp: every kind of attrs of ralle_times_model, and two keys whose copies differ in expiry.
 
+A second, smaller plant (_ones_plant) puts stored hashes of all ones -- in the 16 sorted bits, and ~0
+itself -- at the end of the participants' sorted column, next to the pairs of four non-participants.
+
 Keys run from 9 to 57 bytes, one to four 16-byte chunks of the compare.  The CPU tests state why
 a device test on this stream cannot pass for the wrong reason: the model's lookup is "feed the
 blobs in order, the last one wins", and every blob the kernel must not choose would have given
@@ -315,6 +318,56 @@ def test_sizes(cuda, oracle, n):
         _got, want = fm.find_against_model(cuda, oracle, buf, off, queries, f"n {n}, variant {variant}, hashes {hashes}",
                                            hashes=hashes, variant=variant, shift=shift, key_shift=16 - shift, tail_pad=0)
         assert want[3][0] == 2 * n and want[3][1] >= n
+
+
+def _ones_plant(oracle):
+    """(blobs, consider, queries, h1, h2): 40 blobs (16 sorted bits).  Blob 4 stores its hash with the
+    low 16 bits set, blob 9 -- another key of the same length -- the same hash and subhash, blob 20
+    stores ~0 and blob 30, again another key of that length, ~0 with blob 20's subhash.  Blobs 2, 11,
+    25 and 33 take no part (masked, bad span, no key, key range outside): the compact lays them out as
+    (~0, kNone) behind blobs 20 and 30.  The queries: the keys of blobs 4, 9, 20 and 30 under the
+    stored hashes, a key no blob has under ~0 and blob 20's subhash, and blob 25's key under ~0."""
+    keys = [b"ones-%02d-" % i + b"x" * 11 for i in range(40)]
+    blobs = dm.blobs_of(oracle, keys, [_value(i) for i in range(40)], None, None)
+    h4 = rm.get(blobs[4], 0, rm.F_HASH) | 0xFFFF
+    dm.set_hash(blobs[4], h4)
+    dm.set_hash(blobs[9], h4, rm.get(blobs[4], 0, rm.F_SUBHASH))
+    dm.set_hash(blobs[20], NONE)
+    dm.set_hash(blobs[30], NONE, rm.get(blobs[20], 0, rm.F_SUBHASH))
+    consider = np.ones(40, np.uint8)
+    for i, how in zip((2, 11, 25, 33), dh.BREAKS):
+        blobs[i] = dh.broken(blobs[i], how)
+        consider[i] = how != "masked"
+    queries = [keys[4], keys[9], keys[20], keys[30], b"ones-no-" + b"x" * 11, keys[25]]
+    s4, s20 = rm.get(blobs[4], 0, rm.F_SUBHASH), rm.get(blobs[20], 0, rm.F_SUBHASH)
+    h1 = np.array([h4, h4, NONE, NONE, NONE, NONE], np.uint64)
+    h2 = np.array([s4, s4, s20, s20, s20, rm.get(blobs[25], 0, rm.F_SUBHASH)], np.uint64)
+    return blobs, consider, queries, h1, h2
+
+
+def test_ones_plant_in_the_model(oracle):
+    blobs, consider, queries, h1, h2 = _ones_plant(oracle)
+    buf, off = rm.join(blobs)
+    data, koff = fm.csr(queries)
+    match, status, hit, counts = fm.find_model(buf, off, data, koff, h1, h2, consider=consider)
+    assert match.tolist() == [4, 9, 20, 30, NONE, NONE] and counts == [6, 4, 0]
+    parts = [i for i, _f in fm.participants(buf, off, consider=consider)]
+    assert len(parts) == 36 and len(blobs) <= 256
+    sorted_low = sorted(rm.get(blobs[i], 0, rm.F_HASH) & 0xFFFF for i in parts)
+    assert sorted_low[-4:] == [0xFFFF] * 4 and sorted_low[-5] < 0xFFFF      # the four end the participants' column
+
+
+@pytest.mark.gpu
+def test_hashes_of_all_ones_next_to_non_participants(cuda, oracle):
+    """Stored hashes whose sorted bits are all set, and ~0 itself, sort to the end of the participants,
+    where the compact's (~0, kNone) pairs of the four non-participants follow: the search runs over
+    [0, participants), and a miss under ~0 ends in the run without reading a kNone entry's side."""
+    blobs, consider, queries, h1, h2 = _ones_plant(oracle)
+    buf, off = rm.join(dm.at_odd_offsets(blobs, 6))
+    for shift in (0, 13):
+        _got, want = fm.find_against_model(cuda, oracle, buf, off, queries, f"ones plant, shift {shift}", hashes=(h1, h2),
+                                           consider=consider, shift=shift, key_shift=16 - shift)
+        assert want[0].tolist() == [4, 9, 20, 30, NONE, NONE] and want[3] == [6, 4, 0]
 
 
 @pytest.mark.gpu

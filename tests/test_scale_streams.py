@@ -2,7 +2,8 @@
 from its columns is the pinned model's answer (at sizes where the per-blob models are quick, on both
 sides of the library sort's one-block size; the same code path as at a million), that the tiled
 blobs and records are the per-blob builders' bytes, that the streams hold what the GPU tests of
-tests/test_sort_regimes.py need them to hold at the size those tests use, that this size is where
+tests/test_sort_regimes.py and tests/test_find_regimes.py need them to hold at the size those tests
+use (the queries of the find tests among them: find_expect against ralle_find_model), that this size is where
 the library sort changes its algorithm, and that an expectation built on "any later copy" in place
 of "the nearest" is another one, so those tests would notice an unstable sort.
 """
@@ -12,9 +13,11 @@ import pytest
 import archive_fold_model as af
 import ralle_dedup_model as dm
 import ralle_diff_model as fm
+import ralle_find_model as ffm
 import ralle_subkeys_model as sm
+import ralle_times_model as tm
 import scale_streams as ss
-from scale_streams import N_LARGE, N_SMALL, NONE
+from scale_streams import M32, N_LARGE, N_SMALL, NONE
 
 
 def first_difference(got, want, names, what):
@@ -98,6 +101,22 @@ def test_fold_expectation_is_the_model(oracle, n):
     got = ss.fold_expect(c)
     first_difference(got[:2], want[:2], ("keep", "by"), f"fold {n}")
     assert got[2] == want[2] > n // 12
+
+
+@pytest.mark.parametrize("n", N_SMALL)
+def test_find_expectation_is_the_model(oracle, n):
+    """Under the stored and under the true hashes, with and without consider, with `now` given."""
+    buf, off, consider, c = ss.dedup_stream(oracle, n, seed=n)
+    m = min(2 * n, 1500)                             # the model is a scan per query
+    q = ss.find_queries(oracle, c, m, seed=n + 4)
+    assert set(np.unique(q.kind)) == set(range(5)) and len(q.bytes) == q.key_off[-1]
+    for name, hashes in (("stored", q.stored), ("true", q.true)):
+        for cons in (consider, None):
+            want = ffm.find_model(buf, off, q.bytes, q.key_off, hashes[0], hashes[1], now=tm.NOW, consider=cons)
+            got = ss.find_expect(c, ss.participants(c, cons is not None), q, hashes, now=tm.NOW)
+            first_difference(got[:3], want[:3], ("match", "status", "hit"), f"find {n}, {name} hashes")
+            assert got[3] == want[3] and want[3][0] == m - (q.kind == ss.Q_EMPTY).sum() and want[3][1] > m // 2
+    assert (ss.FIND_PART, ss.FIND_FOUND, ss.FIND_ATTRS, ss.FIND_EXPIRED) == (ffm.PART, ffm.FOUND, ffm.ATTRS, ffm.EXPIRED)
 
 
 # ------------------------------------------------------- the tiled bytes are the builders' bytes
@@ -215,6 +234,46 @@ def test_large_fold_log_is_what_it_claims(oracle):
     assert keep[hot[0]] == 1 and keep[hot[-1]] == 1 and not keep[hot[1:-1]].any()    # the head waits for the chain's end
     assert dropped > N_LARGE // 5 and len(data) < 160 << 20 and h1.dtype == np.uint64
     assert (h1[c.bad == 0] != c.h_true[c.bad == 0]).sum() > 3_000
+
+
+def test_large_find_queries_are_what_they_claim(oracle, large_columns):
+    """What tests/test_find_regimes.py needs of its queries over the dedup stream, counted on the
+    expectation (the figure behind each bound is what this seed gives)."""
+    c, m = large_columns, ss.M_LARGE
+    assert ss.FIND_SEEDS[0] == 1                                                     # large_columns is that stream
+    q = ss.find_queries(oracle, c, m, seed=ss.FIND_SEEDS[1])
+    part = ss.participants(c)
+    match, status, hit, counts = ss.find_expect(c, part, q, q.stored)
+    found, from_blob = (status & ss.FIND_FOUND) != 0, q.pick >= 0
+    assert set((q.key_off[:-1] % np.uint64(16)).tolist()) == set(range(16))          # every CSR start
+    assert m % 256 and m > 4096 and -(-m // 64) > 64 * 64                            # the counter lines wrap
+    assert counts == [m - 100, int(found.sum()), 0] and counts[1] > m * 9 // 10      # 244,238
+    first = ss.find_expect(c, part, q, q.stored, later="first")
+    assert (first[0] != match).sum() > 10_000 and (first[0][~found] == NONE).all()   # 100,552
+    assert not ((first[1] ^ status) & (0xFF ^ ss.FIND_ATTRS)).any() and (first[2] != hit).sum() > 10_000
+    later = found & from_blob
+    assert (match[later].astype(np.int64) > q.pick[later]).sum() > 10_000            # 55,127
+    assert (found & ((q.stored[0] & M32) == M32)).sum() >= 500                       # 3,662
+    assert (found & (q.stored[0] == NONE)).sum() >= 2                                # 5
+    true = ss.find_expect(c, part, q, q.true)
+    assert (found & ((true[1] & ss.FIND_FOUND) == 0)).sum() >= 1_000                 # 6,682
+    assert ((true[1][q.kind == ss.Q_FRESH] & ss.FIND_FOUND) == 0).all() and true[3][1] > m * 8 // 10
+    out = (q.kind == ss.Q_PICK) & ~part[np.maximum(q.pick, 0)]
+    assert (out & found).sum() >= 500 and (out & ~found).sum() >= 500                # 890 and 1,478
+    near = q.kind == ss.Q_NEAR
+    assert near.sum() > 8_000 and not found[near].any()
+    assert ((status & ss.FIND_ATTRS) != 0).sum() >= 10_000                           # 35,975
+    # without consider the masked blobs take part: another expectation
+    assert (ss.find_expect(c, ss.participants(c, False), q, q.stored)[0] != match).sum() > 100
+
+
+def test_runs_of_sorted_bits_hold_other_hashes(oracle):
+    """Neighbours of the sorted column that share their sorted bits under different full hashes, the
+    entries find's backward walk steps over by `hq != h`: 399 at 65,536 blobs (24 sorted bits), 14 at
+    256 (16 bits)."""
+    for n, bits, least in ((65536, 24, 100), (256, 16, 1)):
+        c = ss.ralle_columns(oracle, n, seed=n)
+        assert ss.sort_bits(n) == bits and ss.shared_sorted_bits(c, ss.participants(c), bits) >= least
 
 
 # ----------------------------------------------------------------- an unstable sort would show
