@@ -1313,8 +1313,8 @@ int k2h_amd_archive_fold(const void* file, uint64_t size, const k2h_amd_archive_
  * OW_VAL or RENAME; n when there is none.  Such a record with a bad status or consider[i] == 0
  * does not count.  Only the prefix [0, stop) is the log for everything below: records at or
  * behind stop are not applied and leave no trace.  OW_VAL and RENAME are not executed on the
- * device; the caller handles that one record itself and calls again with the rest of the log
- * and this call's output as the held stream.
+ * device by this call; k2h_amd_archive_barrier (section 5d) executes that one record on this
+ * call's output, and the caller calls again with the rest of the log and that stream.
  *
  * Participants.  Record i takes part by the rule of 5b (status 0, type 0..6, key_len >= 1, key
  * range inside [0, size), checked on the device) and also needs consider[i] != 0 and i < stop.
@@ -1407,6 +1407,112 @@ int k2h_amd_archive_apply(const void* held, uint64_t held_size, const uint64_t* 
                           uint64_t* counts,         /* host, 7 entries, required */
                           uint64_t* stop,           /* host, required */
                           void* stream);
+
+/* 5d. The barrier record a k2h_amd_archive_apply stopped at, executed on the held stream in
+ * place: OW_VAL (K2HArchive::Save writes one per 10 MiB chunk of a large value, K2HDAccess::Write
+ * logs one per write) and RENAME (K2HShm::Rename, and every overwrite of a table with history).
+ * All pointers are device pointers except result.
+ *
+ * The held stream is an arena.  Blob j is held[held_off[j], held_off[j + 1]) as in 5c; held_size
+ * bytes are in use and held_off[na] == held_size; the allocation has held_cap >= held_size
+ * bytes, held_off room for na + 2 entries and held_keep for na + 1.  An executed call clears
+ * held_keep[j] of EVERY participant copy of the addressed identity, appends at most one blob at
+ * held[held_size ...), writes held_off[na + 1] and sets held_keep[na] = 1.  Nothing else of the
+ * arena is written and no copy of the stream is made: the next k2h_amd_archive_apply takes
+ * na + 1 blobs with this held_keep and compacts the dead copies away, as it does for any
+ * held_keep[j] == 0.  Several barrier calls may follow each other on one arena.
+ *
+ * Matching.  Identity and participation of held blobs are those of 5c (a good span, a header that
+ * is not EMPTY, NO_KEY or BAD_RANGE, held_keep[j] != 0; stored hash, subhash, key length, then key
+ * bytes); the deciding blob is the LAST participant of the identity.  Record b's old key is
+ * looked up under h1[b] / h2[b], a RENAME's new key (its exdata range) under new_h1[b] /
+ * new_h2[b].  The four arrays have n entries each and are given together or not at all; without
+ * them the call hashes what it needs (K2H_AMD_FLAG_STD_FNV chooses the seed).  The values end up
+ * in the appended header, as in 5c.
+ *
+ * Record b must have status == 0, consider[b] != 0 (consider NULL: every record), type OW_VAL or
+ * RENAME, key_len >= 1 and its key range inside [0, size): otherwise NOT_A_BARRIER.
+ *
+ * result[0], the outcome.  Anything but EXECUTED changes nothing on the device.
+ *   K2H_AMD_BARRIER_EXECUTED
+ *   K2H_AMD_BARRIER_NOT_FOUND      RENAME: no participant has the old identity (Load fails the
+ *                                  record, lib/k2hshm.cc:3389-3392)
+ *   K2H_AMD_BARRIER_NEW_EXISTS     RENAME: a participant holds the new identity and the new key's
+ *                                  bytes are not the old key's.  Refused: Rename does not look for
+ *                                  a live element under the new key, InsertElement
+ *                                  (lib/k2hshm.cc:1279-1316) appends the renamed one behind it and
+ *                                  GetElement (:1196-1212) goes on finding the older one, so the
+ *                                  table holds two elements under one key -- a state no stream can
+ *                                  express, because in a stream the last copy wins.
+ *   K2H_AMD_BARRIER_BAD_RECORD     RENAME: exdata_len == 0 (:3366) or its range outside the file.
+ *                                  OW_VAL: exdata_len not in 1..8, offset < 0
+ *                                  (lib/k2hdaccess.cc:266), val_len == 0 (:394), or the val or
+ *                                  exdata range outside the file.  Known differences: for
+ *                                  val_len == 0 the reference has created the key and stretched
+ *                                  the value before it fails, this call has no side effect; an
+ *                                  exdata of more than 8 bytes overflows OWVAL_EXDATA
+ *                                  (lib/k2hcommand.h:90-93) on the reference's stack.
+ *   K2H_AMD_BARRIER_NOT_A_BARRIER
+ * For NOT_FOUND before NEW_EXISTS: Rename fails on the missing old key first.
+ *
+ * RENAME (lib/k2harchive.cc:361-362, lib/k2hshm.cc:3364-3502), executed: the appended blob has the
+ * new key, new_h1[b] / new_h2[b], and the value and subkeys of the deciding old blob; its attrs
+ * are the record's when attrs_len > 0 and the range is inside the file, otherwise the old blob's
+ * (:3427-3436).  A new key with the same bytes as the old one is executed like any other.
+ *
+ * OW_VAL (lib/k2harchive.cc:343-360, lib/k2hdaccess.cc:168-455), executed: the offset is the
+ * exdata's 1..8 bytes over a zeroed off_t, little-endian.  After b the call absorbs the records
+ * b + 1, b + 2, ... while each is a considered, status-0 OW_VAL with the same key length and key
+ * bytes that is no BAD_RECORD, up to K2H_AMD_BARRIER_MAX_RUN records in all; the first record
+ * that fails a test ends the run and is left alone.  The value is what the run's writes leave
+ * when executed in log order: its length is the maximum of the old length and every
+ * offset + val_len, and where writes overlap the later one wins.  A byte that neither a write nor
+ * the old value covers is written as ZERO and the call is flagged K2H_AMD_BARRIER_GAP: the
+ * reference stretches the value without initialising it (lib/k2hdaccess.cc:260-262, :336-351,
+ * lib/k2hpagemem.cc:471-475), so those bytes are undefined there and zero is this library's
+ * choice.  Subkeys and attrs are the deciding blob's.  A key that is not held is created
+ * (K2HDAccess::Open, Set(key, NULL, 0)): no old value, no subkeys, no attrs, flagged
+ * K2H_AMD_BARRIER_CREATED -- under 5b's precondition of a table without builtin attributes.
+ *
+ * The appended blob is in GetElementToBinary's layout as 5c's part 2 is: 80 bytes plus the four
+ * segment lengths, the running positions written for empty segments too.  Segment bytes are
+ * read from wherever the deciding blob puts them, permuted, gapped or overlapping.
+ *
+ *   result  (host, 8 entries, required) [0] the outcome; [1] records executed -- the caller
+ *           continues at b + result[1]; [2] bytes appended; [3] K2H_AMD_BARRIER_CREATED |
+ *           K2H_AMD_BARRIER_GAP; [4] held copies cleared; [5] the deciding blob's index, or
+ *           UINT64_MAX; [6] the final value length; [7] reserved, 0.  Any outcome but EXECUTED:
+ *           [1..4], [6] and [7] are 0 and [5] is UINT64_MAX.
+ *
+ * With K2H_AMD_BARRIER_COUNT_ONLY nothing on the device is written and result is complete.
+ * Without it, result[2] > held_cap - held_size returns K2H_AMD_EINVAL with result set and nothing
+ * written, held_keep included.  `stream` is synchronised exactly once per call, to return result.
+ * K2H_AMD_EINVAL, judged on the host before any device is touched, each with its own message:
+ * result NULL; held_keep NULL; held or held_off NULL with na > 0 (or without COUNT_ONLY); file or
+ * recs NULL; b >= n; held_cap < held_size; the four hash arrays neither all given nor all NULL;
+ * unknown flags; K2H_AMD_FLAG_STD_FNV with the hashes given; na > 2^32 - 2.
+ *
+ * Memory rule as in 5c; all absolute offsets are 64-bit.  Temporary device memory, kept per
+ * device between calls: 4 bytes per held blob and about 8 KiB. */
+#define K2H_AMD_BARRIER_EXECUTED 0u
+#define K2H_AMD_BARRIER_NOT_FOUND 1u
+#define K2H_AMD_BARRIER_NEW_EXISTS 2u
+#define K2H_AMD_BARRIER_BAD_RECORD 3u
+#define K2H_AMD_BARRIER_NOT_A_BARRIER 4u
+#define K2H_AMD_BARRIER_CREATED 1u
+#define K2H_AMD_BARRIER_GAP 2u
+#define K2H_AMD_BARRIER_COUNT_ONLY 0x100u
+#define K2H_AMD_BARRIER_MAX_RUN 256
+
+int k2h_amd_archive_barrier(void* held, uint64_t held_size, uint64_t held_cap, uint64_t* held_off, uint64_t na,
+                            uint8_t* held_keep,            /* na + 1, in/out, required */
+                            const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n,
+                            uint64_t b,                    /* the record to execute, b < n */
+                            const uint8_t* consider,       /* n, or NULL: every record */
+                            const uint64_t* h1, const uint64_t* h2, const uint64_t* new_h1, const uint64_t* new_h2,
+                            uint32_t flags,                /* K2H_AMD_FLAG_STD_FNV | K2H_AMD_BARRIER_COUNT_ONLY */
+                            uint64_t* result,              /* host, 8 entries, required */
+                            void* stream);
 
 /* k2himport inputs (tests/k2himport.cc:74-117): k2h_amd_import_scan splits a TSV
  * (key TAB value NEWLINE) or mdbm_export file (five header lines ending "HEADER=END",

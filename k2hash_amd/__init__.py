@@ -21,6 +21,8 @@ and (2) a batch C ABI backed by hand-written gfx950 HIP kernels (section 2).
              the records that still matter under Load's rule (fold_device, compact_device)
   apply      a transaction log applied to a held blob stream: replication, and log -> snapshot
              (apply_log, apply_records)
+  barrier    the OW_VAL and RENAME records an apply stops at, executed on the held stream in
+             place, and a whole log replayed with them (execute_barrier, replay_log)
   delta      the inverse: from a held and a new blob stream to the transaction log that turns
              the one into the other (delta_log, delta_records)
   find       keys looked up in a held blob stream: the stream indexed once, a batch of keys found
@@ -34,6 +36,7 @@ from .batch import (bucket_index, hash_csr, hash_csr_host, hash_csr_index, hash_
                     hash_fixed_index, synth_bytes, synth_offsets, unpack_kindex, version)
 from .apply import Applied, apply_log, apply_records
 from .archive import compact_device, fold_device
+from .barrier import Executed, Replayed, execute_barrier, replay_log
 from .delta import Delta, delta_log, delta_records
 from .find import Found, StreamIndex, fetch_segments, find_keys, get_values, index_stream
 from .ralledata import (Diff, HashRange, Times, TimeWindow, archive_to_ralledata, blob_times, check_ralledata,
@@ -52,6 +55,6 @@ __all__ = [
     "blob_times", "TimeWindow", "Times", "fold_device", "compact_device", "diff_ralledata", "Diff",
     "subkey_edges", "reach_subkeys", "subtree_ralledata", "SubkeyEdges", "Reach",
     "drop_mask", "unlink_subkeys", "prune_ralledata", "Unlinked", "apply_log", "apply_records", "Applied",
-    "delta_log", "delta_records", "Delta",
+    "delta_log", "delta_records", "Delta", "execute_barrier", "replay_log", "Executed", "Replayed",
     "index_stream", "find_keys", "fetch_segments", "get_values", "StreamIndex", "Found",
 ]

@@ -86,6 +86,10 @@ K2H_AMD_DIFF_ATTRS, K2H_AMD_DIFF_DATA, K2H_AMD_DIFF_REPEAT, K2H_AMD_DIFF_APPLY =
 K2H_AMD_SKEY_PART, K2H_AMD_SKEY_HAS, K2H_AMD_SKEY_BAD = 0x1, 0x2, 0x4
 K2H_AMD_UNLINK_REWRITTEN, K2H_AMD_UNLINK_EMPTIED, K2H_AMD_UNLINK_KEY_ONLY = 0x1, 0x2, 0x4
 K2H_AMD_APPLY_TOUCHED, K2H_AMD_APPLY_SUPERSEDED, K2H_AMD_APPLY_LEFT_OUT = 1, 2, 3
+K2H_AMD_BARRIER_EXECUTED, K2H_AMD_BARRIER_NOT_FOUND, K2H_AMD_BARRIER_NEW_EXISTS = 0, 1, 2
+K2H_AMD_BARRIER_BAD_RECORD, K2H_AMD_BARRIER_NOT_A_BARRIER = 3, 4
+K2H_AMD_BARRIER_CREATED, K2H_AMD_BARRIER_GAP = 1, 2
+K2H_AMD_BARRIER_COUNT_ONLY, K2H_AMD_BARRIER_MAX_RUN = 0x100, 256
 K2H_AMD_DELTA_SET_ALL, K2H_AMD_DELTA_REPLACE_VAL, K2H_AMD_DELTA_REPLACE_SKEY = 0x01, 0x02, 0x04
 K2H_AMD_DELTA_REPLACE_ATTRS, K2H_AMD_DELTA_DEL_KEY = 0x08, 0x10
 K2H_AMD_FIND_PART, K2H_AMD_FIND_FOUND, K2H_AMD_FIND_ATTRS, K2H_AMD_FIND_EXPIRED = 0x01, 0x02, 0x04, 0x08
@@ -150,6 +154,8 @@ SIGNATURES = {
     "k2h_amd_archive_fold": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _p, _u64p, _p]),
     "k2h_amd_archive_apply": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _p, _p, _p, ctypes.c_uint32,
                                              _p, _u64, _p, _p, _p, _u64p, _u64p, _p]),
+    "k2h_amd_archive_barrier": (ctypes.c_int, [_p, _u64, _u64, _p, _u64, _p, _p, _u64, _p, _u64, _u64, _p, _p, _p, _p, _p,
+                                               ctypes.c_uint32, _u64p, _p]),
     "k2h_amd_import_scan": (ctypes.c_int, [_p, _u64, ctypes.c_int, _p, _u64, _p]),
     "k2h_amd_import_prehash_host": (ctypes.c_int, [_p, _u64, _p, _u64, _p, _p, ctypes.c_uint32, ctypes.c_int]),
     "k2h_amd_import_scan_device": (ctypes.c_int, [_p, _u64, ctypes.c_int, _p, _u64, _p, _p]),

@@ -6,9 +6,10 @@ empty held stream it turns a log with REPLACE_* and DEL_KEY records into a snaps
 archive_to_ralledata (SET_ALL only) cannot.  delta.delta_log is the inverse: from the held and the new
 stream to the log that, applied here, gives the new stream's elements.
 
-OW_VAL and RENAME are not executed on the device.  The first of them ends the log: ``stop`` is
-its index.  The caller handles that one record itself and calls again with the rest and this
-call's output as the held stream (INTEGRATION.md has the loop).
+OW_VAL and RENAME are not executed by these calls.  The first of them ends the log: ``stop`` is
+its index.  barrier.execute_barrier (include/k2hash_amd.h section 5d) executes that one record on
+this call's output, and the caller calls again with the rest and that stream; barrier.replay_log
+is the loop (INTEGRATION.md shows it).
 
 The ``stream`` argument is that of batch.py's module docstring: None means the current torch
 stream; otherwise every device operation of the call, the wrappers' own torch ops included, is

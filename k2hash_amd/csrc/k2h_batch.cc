@@ -743,6 +743,43 @@ __attribute__((visibility("default"))) int k2h_amd_archive_apply(
   return rc == K2H_AMD_OK ? rc : fail(rc, "launch_archive_apply", e);
 }
 
+// Section 5d: the barrier record at b executed on the held arena.  Judged on the host like the two above.
+__attribute__((visibility("default"))) int k2h_amd_archive_barrier(
+    void* held, uint64_t held_size, uint64_t held_cap, uint64_t* held_off, uint64_t na, uint8_t* held_keep,
+    const void* file, uint64_t size, const k2h_amd_archive_rec* recs, uint64_t n, uint64_t b, const uint8_t* consider,
+    const uint64_t* h1, const uint64_t* h2, const uint64_t* new_h1, const uint64_t* new_h2, uint32_t flags,
+    uint64_t* result, void* stream) {
+  if (!result) return fail(K2H_AMD_EINVAL, "archive_barrier: NULL result");
+  for (int k = 0; k < 8; ++k) result[k] = 0;
+  result[0] = K2H_AMD_BARRIER_NOT_A_BARRIER;
+  result[5] = ~0ull;
+  if (!held_keep) return fail(K2H_AMD_EINVAL, "archive_barrier: NULL held_keep");
+  if (na && !held) return fail(K2H_AMD_EINVAL, "archive_barrier: NULL held");
+  if (na && !held_off) return fail(K2H_AMD_EINVAL, "archive_barrier: NULL held_off");
+  if (!file) return fail(K2H_AMD_EINVAL, "archive_barrier: NULL file");
+  if (!recs) return fail(K2H_AMD_EINVAL, "archive_barrier: NULL recs");
+  if (b >= n) return fail(K2H_AMD_EINVAL, "archive_barrier: b is not below n");
+  if (held_cap < held_size) return fail(K2H_AMD_EINVAL, "archive_barrier: held_cap is below held_size");
+  const int given = !!h1 + !!h2 + !!new_h1 + !!new_h2;
+  if (given != 0 && given != 4)
+    return fail(K2H_AMD_EINVAL, "archive_barrier: h1, h2, new_h1 and new_h2 are given together or not at all");
+  if (flags & ~(K2H_AMD_FLAG_STD_FNV | K2H_AMD_BARRIER_COUNT_ONLY)) return fail(K2H_AMD_EINVAL, "archive_barrier: unknown flags");
+  if ((flags & K2H_AMD_FLAG_STD_FNV) && given)
+    return fail(K2H_AMD_EINVAL, "archive_barrier: K2H_AMD_FLAG_STD_FNV chooses the hash only when the hashes are NULL");
+  if (na > 0xFFFFFFFEull)
+    return fail(K2H_AMD_EINVAL, "archive_barrier: more than 2^32 - 2 blobs (indices are kept as 32-bit values)");
+  const bool count_only = (flags & K2H_AMD_BARRIER_COUNT_ONLY) != 0;
+  if (!count_only && (!held || !held_off))
+    return fail(K2H_AMD_EINVAL, "archive_barrier: NULL held or held_off without K2H_AMD_BARRIER_COUNT_ONLY");
+  K2H_GATE();
+  hipError_t e = hipSuccess;
+  int rc = k2h::launch_archive_barrier(held, held_size, held_cap, held_off, na, held_keep, file, size, recs, n, b,
+                                       consider, h1, h2, new_h1, new_h2, seed_for(flags), count_only, result,
+                                       (hipStream_t)stream, &e);
+  if (rc == K2H_AMD_EINVAL) return exceeds_cap("archive_barrier", "appended blob", result[2], held_cap - held_size);
+  return rc == K2H_AMD_OK ? rc : fail(rc, "launch_archive_barrier", e);
+}
+
 // ---------------------------------------------------------------------------
 // RALLEDATA producer (include/k2hash_amd.h section 4)
 // ---------------------------------------------------------------------------

@@ -281,6 +281,17 @@ int launch_archive_apply(const void* held, uint64_t held_size, const uint64_t* h
                          void* out, uint64_t out_cap, uint64_t* out_off, uint64_t* origin, uint8_t* touched,
                          uint64_t* counts, uint64_t* stop, hipStream_t stream, hipError_t* herr);
 
+// A barrier record executed on a held arena in place (k2h_archive_barrier.hip).  Returns a
+// K2H_AMD_* code (the HIP error in *herr) and synchronises the stream once, to return result.
+// na <= 2^32 - 2, b < n, held_cap >= held_size; the four hash arrays all given or all NULL (then
+// record b's are hashed with `seed`).  K2H_AMD_EINVAL: an executed outcome whose result[2] exceeds
+// held_cap - held_size (result is filled, nothing on the device is written).
+int launch_archive_barrier(void* held, uint64_t held_size, uint64_t held_cap, uint64_t* held_off, uint64_t na,
+                           uint8_t* held_keep, const void* file, uint64_t size, const k2h_amd_archive_rec* recs,
+                           uint64_t n, uint64_t b, const uint8_t* consider, const uint64_t* h1, const uint64_t* h2,
+                           const uint64_t* new_h1, const uint64_t* new_h2, uint64_t seed, bool count_only,
+                           uint64_t* result, hipStream_t stream, hipError_t* herr);
+
 // S_p = seed * P^-p (p = 0..15): start states for end-aligned chunking (k2h_csr.hip).
 struct SpadTable {
   uint64_t v[16];
